@@ -14,6 +14,12 @@ RCCL all_gather of the 264-byte proof records (the only exchange the path has). 
 weak (every rank proves its own batch of --batch proofs, the headline configuration);
 --scaling strong splits ONE global batch of --batch proofs across the ranks (BASELINE configs 3 and
 4: --workload verifier --batch 4096, --workload elgamal-add --batch 8192).
+
+A plain run times the headline only: set-up, --warmup steps, --steps timed steps, the JSON line.
+--full adds the secondary legs: the worst-case witnesses (--worst-case-steps), the bounded-memory
+operating point (--bounded-gb), the CPU baseline (--cpu-sample) and the field-multiply
+microbenchmark; a leg's own option given explicitly turns that leg on without --full.
+--dump-outputs DIR writes what the last timed step computed (proof records, status) as .npy files.
 """
 import argparse
 import json
@@ -231,6 +237,8 @@ def bench_plonk(args):
     for _ in range(args.steps):
         rec, status = prover.prove_raw(inp, blind)
     elapsed = time.perf_counter() - ts
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"proofs": rec, "status": status})
     proofs = prover.proofs_of(rec[:1])
     n_pub = pk.n_public
     rinv = pow(1 << 256, workloads.R - 2, workloads.R)
@@ -248,6 +256,30 @@ def bench_plonk(args):
     print(json.dumps(out))
     prover.close()
     ctx.close()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, suffix=""):
+    """--dump-outputs: every array as d/<name><suffix>.npy in float64.  64-bit integer arrays (proof
+    records, Montgomery limbs) are split into 32-bit words first, which float64 holds exactly; if
+    the whole would pass DUMP_LIMIT_BYTES, the same seeded sample of rows is taken from each."""
+    os.makedirs(d, exist_ok=True)
+    outs = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype.kind in "iu" and a.dtype.itemsize == 8:
+            a = a.view(np.uint32)
+        outs[name] = a.astype(np.float64)
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = min(a.shape[0] for a in outs.values())
+        keep = max(1, n * DUMP_LIMIT_BYTES // total)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        outs = {k: a[rows] for k, a in outs.items()}
+    for name, a in outs.items():
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), a)
 
 
 class stdout_to_stderr:
@@ -298,7 +330,7 @@ def rank_jobs(args, rank, world):
     else:
         B = args.batch
     n_distinct = min(B, args.distinct) if args.distinct > 0 else B
-    wc_steps = args.worst_case_steps if args.worst_case_steps >= 0 else args.steps
+    wc_steps = args.worst_case_steps
     if args.workload != "arbo" or args.populated >= args.levels - 1:
         wc_steps = 0
     jobs = [("main", 1000 + rank, n_distinct, args.populated)]
@@ -365,8 +397,9 @@ def main():
     ap.add_argument("--populated", type=int, default=10, help="non-zero siblings per path")
     ap.add_argument("--window-g1", type=int, default=0)
     ap.add_argument("--window-g2", type=int, default=0)
-    ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="proofs for the CPU baseline (-1: 2 per core, then more up to ~15 s of CPU work; 0: skip)")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="proofs for the CPU baseline (-1: 2 per core, then more up to ~15 s of CPU "
+                         "work; 0: skip); default -1 under --full, else 0")
     ap.add_argument("--dist-backend", default="nccl",
                     help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--device", type=int, default=-1,
@@ -378,9 +411,10 @@ def main():
                          "per-step all_gather -- rehearsal of the N > 1 path on a one-GPU box")
     ap.add_argument("--no-gather", action="store_true",
                     help="skip the per-step all_gather of proof records (N > 1)")
-    ap.add_argument("--worst-case-steps", type=int, default=-1,
+    ap.add_argument("--worst-case-steps", type=int, default=None,
                     help="arbo only: extra timed steps on witnesses with every level populated "
-                         "(every wire differs between lanes); -1: as many as --steps, 0: skip")
+                         "(every wire differs between lanes); -1: as many as --steps, 0: skip; "
+                         "default -1 under --full, else 0")
     ap.add_argument("--gen-workers", type=int, default=0, help="witness generator processes")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="one blocking zkmi_prove_batch per step (no overlap of consecutive steps)")
@@ -407,9 +441,10 @@ def main():
     ap.add_argument("--table-budget-gb", type=float, default=0.0,
                     help="zkmi_pk_desc.table_budget_bytes: cap for the key's MSM tables (0 = "
                          "whatever the free HBM allows); the bounded-memory operating points")
-    ap.add_argument("--bounded-gb", type=float, default=64.0,
+    ap.add_argument("--bounded-gb", type=float, default=None,
                     help="after the headline: reload the key with this table budget and time "
-                         "--bounded-steps steps (the bounded-memory operating point; 0 = skip)")
+                         "--bounded-steps steps (the bounded-memory operating point; 0 = skip); "
+                         "default 64 under --full, else 0")
     ap.add_argument("--bounded-steps", type=int, default=8)
     ap.add_argument("--no-cache", action="store_true",
                     help="recompute the compiled circuit and the witnesses instead of using the "
@@ -418,8 +453,24 @@ def main():
                     help="launcher / process-group rehearsal for boxes without a GPU: everything "
                          "but the GPU work (compile, witnesses, rendezvous, barriers, per-step "
                          "all_gather of zeroed records); prints value null and \"rehearsal\": true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs: worst-case witnesses, bounded-memory operating "
+                         "point, CPU baseline, field-multiply microbenchmark")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (proof records, "
+                         "status) to DIR/<name>.npy as float64")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
+    if args.cpu_sample is None:
+        args.cpu_sample = -1 if args.full else 0
+    if args.worst_case_steps is None:
+        args.worst_case_steps = -1 if args.full else 0
+    if args.worst_case_steps < 0:
+        args.worst_case_steps = args.steps
+    if args.bounded_gb is None:
+        args.bounded_gb = 64.0 if args.full else 0.0
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus or 1) > 1:
         return launch_ranks(args)
@@ -454,8 +505,7 @@ def main():
         B, global_batch = args.batch, args.batch * world
     n_distinct = min(B, args.distinct) if args.distinct > 0 else B
     jobs = rank_jobs(args, rank, world)
-    wc_steps = (args.worst_case_steps if args.worst_case_steps >= 0 else args.steps) \
-        if len(jobs) > 1 and args.entry == "inputs" else 0
+    wc_steps = args.worst_case_steps if len(jobs) > 1 and args.entry == "inputs" else 0
     t1 = time.time()
     sets = generate_witnesses(cc, args.workload, args.levels, jobs, args.gen_workers or
                               max(1, min(16, host_cpus() // world)), use_cache)
@@ -631,6 +681,11 @@ def main():
         dist.all_reduce(t)
         n_bad = int(t.item())
     proofs = proofs_d.cpu().numpy().view(np.uint64)
+    if args.dump_outputs:
+        outs = {"proofs": proofs, "status": status}
+        if coms_d is not None:
+            outs["commitments"] = coms_d.cpu().numpy().view(np.uint64)
+        dump_outputs(args.dump_outputs, outs, "" if world == 1 else f"_rank{rank}")
     gather_ok = None
     if gather:
         gp, gs = gathered[0]
@@ -719,10 +774,11 @@ def main():
             roofline["alu"]["frac"] = None
             roofline["alu"]["note"] = ("subset-sum tables: zero digits are skipped, `achieved` "
                                        "counts every (group, window) and is an upper bound")
-        try:
-            roofline["alu"]["fq_mul_per_s_ff29_microbench"] = ctx.field_mul_bench(2, 1 << 22, 256)
-        except Exception:
-            pass
+        if args.full:
+            try:
+                roofline["alu"]["fq_mul_per_s_ff29_microbench"] = ctx.field_mul_bench(2, 1 << 22, 256)
+            except Exception:
+                pass
         cpu = None
         if args.cpu_sample != 0 and world == 1:      # CPU baseline: rank 0 at N = 1 only
             from oracle import cref

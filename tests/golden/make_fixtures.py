@@ -37,9 +37,58 @@ def poseidon():
             for c in cases]
 
 
+def mimc7_constants():
+    """mimc7_reference_constants.json -- the 90 round constants of the reference's MiMC7 tables
+    (hash/native/bn254/mimc7/constants.go, hash/emulated/bn254/mimc7/constants.go), extracted as
+    data by regex; the emulated file also holds the field modulus, which is dropped."""
+    out = {}
+    for name, rel in (("native", "hash/native/bn254/mimc7/constants.go"),
+                      ("emulated", "hash/emulated/bn254/mimc7/constants.go")):
+        vals = re.findall(r'"(\d{20,})"', open(os.path.join(REF, rel)).read())
+        out[name] = [v for v in vals if int(v) != pyref.R]
+        assert len(out[name]) == 90, (name, len(out[name]))
+    return out
+
+
+def table_digest(vals):
+    """SHA-256 of a list of integers written in decimal and joined by ','"""
+    import hashlib
+    return hashlib.sha256(",".join(str(int(v)) for v in vals).encode()).hexdigest()
+
+
+def poseidon_tables():
+    """poseidon_reference_tables.json -- the reference's optimised Poseidon tables
+    (hash/native/bn254/poseidon/constants.go: strC, strM, strS, strP; 2 MB of decimal text) recorded
+    as digests: for every width t = 2..17 the length and table_digest() of that width's slice of
+    each table, and each table's total length."""
+    from gnark_crypto_primitives_amd.hash.poseidon_constants import N_ROUNDS_P
+    src = open(os.path.join(REF, "hash/native/bn254/poseidon/constants.go")).read()
+
+    def section(name):
+        i = src.index("var " + name + " =")
+        j = src.find("\nvar ", i + 5)
+        return [int(x) for x in re.findall(r'"(\d+)"', src[i:j if j > 0 else len(src)])]
+    tables = {k: section("str" + k) for k in "CMSP"}
+    off = dict.fromkeys("CMSP", 0)
+    widths = {}
+    for t in range(2, 18):
+        rp = N_ROUNDS_P[t - 2]
+        size = {"C": 8 * t + rp, "M": t * t, "P": t * t, "S": (2 * t - 1) * rp}
+        widths[str(t)] = {}
+        for k in "CMSP":
+            part = tables[k][off[k]:off[k] + size[k]]
+            widths[str(t)][k] = {"n": len(part), "sha256": table_digest(part)}
+            off[k] += size[k]
+    return {"widths": widths, "totals": {k: len(v) for k, v in tables.items()}}
+
+
 if __name__ == "__main__":
     json.dump(chaum_pedersen(), open(os.path.join(HERE, "chaum_pedersen_k3.json"), "w"), indent=1)
     json.dump(poseidon(), open(os.path.join(HERE, "poseidon_kat.json"), "w"), indent=1)
+    json.dump(mimc7_constants(), open(os.path.join(HERE, "mimc7_reference_constants.json"), "w"),
+              indent=1)
+    json.dump(poseidon_tables(), open(os.path.join(HERE, "poseidon_reference_tables.json"), "w"),
+              indent=1)
     print("fixtures written")
 
 

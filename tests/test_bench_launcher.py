@@ -22,7 +22,7 @@ def _run(args, tmp_path, env=None):
 
 
 def test_gpus_2_self_launch_world_2_one_json_line(tmp_path):
-    r = _run(["--gpus", "2"] + SMALL, tmp_path)
+    r = _run(["--gpus", "2", "--full"] + SMALL, tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout

@@ -1,8 +1,8 @@
 """Poseidon: parameter tables, known-answer vectors, gadget vs off-circuit vs textbook oracle."""
+import hashlib
 import json
 import os
 import random
-import re
 
 import pytest
 
@@ -12,7 +12,6 @@ from gnark_crypto_primitives_amd.hash.poseidon_constants import N_ROUNDS_P, opt_
 from oracle import pyref
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF_CONSTANTS = "/root/reference/hash/native/bn254/poseidon/constants.go"
 
 # public circomlib / iden3 vectors
 K1 = 7853200120776062878684798364095072458815029376092732009249414926327459813530
@@ -37,27 +36,28 @@ def test_native_matches_golden_and_oracle():
         assert poseidon_native.hash(ins) == pyref.poseidon_hash(ins)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CONSTANTS), reason="reference tree not present")
-def test_generated_tables_equal_reference_text():
-    """Grain LFSR + optimised-constant derivation reproduce constants.go:48 (C), :2291 (M),
-    :4414 (S), :22733 (P) for every width t = 2..17."""
-    src = open(REF_CONSTANTS).read()
+def _digest(vals):
+    """tests/golden/make_fixtures.py's table_digest: SHA-256 of the decimal values joined by ','"""
+    return hashlib.sha256(",".join(str(int(v)) for v in vals).encode()).hexdigest()
 
-    def section(name):
-        i = src.index("var " + name + " =")
-        j = src.find("\nvar ", i + 5)
-        return [int(x) for x in re.findall(r'"(\d+)"', src[i:j if j > 0 else len(src)])]
-    allc, allm, alls, allp = (section(n) for n in ("strC", "strM", "strS", "strP"))
-    oc = om = os_ = op = 0
+
+def test_generated_tables_equal_reference_text():
+    """Grain LFSR + optimised-constant derivation reproduce the reference's constants.go:48 (C),
+    :2291 (M), :4414 (S), :22733 (P) for every width t = 2..17.  The 2 MB of reference text are
+    recorded in tests/golden/poseidon_reference_tables.json as each width's slice length and
+    digest, and each table's total length."""
+    gold = json.load(open(os.path.join(GOLD, "poseidon_reference_tables.json")))
+    total = dict.fromkeys("CMPS", 0)
     for t in range(2, 18):
         rp = N_ROUNDS_P[t - 2]
         c, m, p, s = opt_params(t)
-        assert allc[oc:oc + 8 * t + rp] == c
-        assert allm[om:om + t * t] == [x for r in m for x in r]
-        assert allp[op:op + t * t] == [x for r in p for x in r]
-        assert alls[os_:os_ + (2 * t - 1) * rp] == s
-        oc, om, op, os_ = oc + 8 * t + rp, om + t * t, op + t * t, os_ + (2 * t - 1) * rp
-    assert (oc, om, op, os_) == (len(allc), len(allm), len(allp), len(alls))
+        assert len(c) == 8 * t + rp and len(s) == (2 * t - 1) * rp
+        got = {"C": c, "M": [x for r in m for x in r], "P": [x for r in p for x in r], "S": s}
+        for k, v in got.items():
+            want = gold["widths"][str(t)][k]
+            assert (want["n"], want["sha256"]) == (len(v), _digest(v)), (t, k)
+            total[k] += len(v)
+    assert total == gold["totals"]
 
 
 def _hash_circuit(n, multi=False):
