@@ -12,8 +12,7 @@ using namespace zk;
 
 namespace zk {
 
-int ensure_scratch(zkmi_ctx* ctx, int slot, size_t bytes, void** out) {
-  DevBuf& s = ctx->scratch[slot];
+int ensure_scratch(zkmi_ctx* ctx, DevBuf& s, size_t bytes, void** out) {
   if (s.bytes < bytes) {
     if (s.p) {
       // nothing queued on any of the context's streams may still use the old buffer
@@ -34,18 +33,17 @@ int ensure_scratch(zkmi_ctx* ctx, int slot, size_t bytes, void** out) {
     }
     s.bytes = bytes;
   }
-  *out = s.p;
+  if (out) *out = s.p;
   return ZKMI_OK;
 }
 
-static bool is_device_ptr(const void* p) {
-  hipPointerAttribute_t attr;
-  hipError_t e = hipPointerGetAttributes(&attr, p);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // clear sticky "invalid value" for plain host memory
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+// Guard of every entry point that is not part of the Groth16 pipeline.  With no batch in flight,
+// nothing on any stream uses set 0's buffers, so after this check those entry points may borrow
+// them (value file, a, b, c, misc) as their own scratch.
+int require_idle(zkmi_ctx* ctx) {
+  if (!ctx->sets[0].pending && !ctx->sets[1].pending) return ZKMI_OK;
+  ctx->err = "a submitted prove batch is in flight; collect it first";
+  return ZKMI_ERR_ARG;
 }
 
 // RAII staging of a caller buffer (host or device) as device memory
@@ -59,7 +57,7 @@ struct Staged {
   int in(const void* p, size_t n) {
     bytes = n;
     if (n == 0) return ZKMI_OK;
-    if (is_device_ptr(p)) {
+    if (pointer_kind(p) == PTR_DEVICE) {
       dev = const_cast<void*>(p);
       return ZKMI_OK;
     }
@@ -71,7 +69,7 @@ struct Staged {
   int out(void* p, size_t n) {
     bytes = n;
     if (n == 0) return ZKMI_OK;
-    if (is_device_ptr(p)) {
+    if (pointer_kind(p) == PTR_DEVICE) {
       dev = p;
       return ZKMI_OK;
     }
@@ -221,6 +219,107 @@ __global__ __launch_bounds__(64) void assemble_g2_kernel(const G2XYZZ* sB2, cons
   out[i].bs = to_affine(BS);
 }
 
+// ---- HBM working set of a pipeline set (zkmi_ctx::ProveSet) -------------------------------------
+// Byte counts used both by the allocation (prove_set_begin) and by the planner
+// (prove_working_set_bytes).  The sums buffer:
+struct SumsView {
+  G1XYZZ *sA, *sB1, *sK, *sZ, *tR, *tS, *tNRS;
+  G2XYZZ *sB2, *tS2;
+  ProofOut* proofs;
+  G1XYZZ* w1[4];   // deferred window sums of A, B1, K, Z ([<= 256][Bp] each)
+  G2XYZZ* w2;
+  SumsView(void* base, size_t Bp) {
+    char* m = (char*)base;
+    sA = (G1XYZZ*)m;   m += Bp * 128;
+    sB1 = (G1XYZZ*)m;  m += Bp * 128;
+    sK = (G1XYZZ*)m;   m += Bp * 128;
+    sZ = (G1XYZZ*)m;   m += Bp * 128;
+    tR = (G1XYZZ*)m;   m += Bp * 128;
+    tS = (G1XYZZ*)m;   m += Bp * 128;
+    tNRS = (G1XYZZ*)m; m += Bp * 128;
+    sB2 = (G2XYZZ*)m;  m += Bp * 256;
+    tS2 = (G2XYZZ*)m;  m += Bp * 256;
+    proofs = (ProofOut*)m;  m += Bp * 256;
+    for (int i = 0; i < 4; i++) {
+      w1[i] = (G1XYZZ*)m;
+      m += 256 * Bp * 128;
+    }
+    w2 = (G2XYZZ*)m;
+  }
+};
+static size_t sums_bytes(size_t Bp) { return Bp * (7 * 128 + 2 * 256 + 256 + 256 * (4 * 128 + 256)); }
+
+// the other buffers of a pipeline set: value file of `value_rows`, a, b, c over the domain of n,
+// misc = r/s (Bp x 96) + status (Bp x 4) + the staging area of `n_staged` input rows and r/s
+struct SetBytes {
+  size_t slots, abc, misc;
+};
+static SetBytes prove_set_bytes(size_t value_rows, size_t n, size_t n_staged, size_t batch, size_t Bp) {
+  return {value_rows * Bp * 32, n * Bp * 32, Bp * (96 + 4) + batch * (n_staged * 32 + 64)};
+}
+
+// a caller array as device memory: used in place, or (host memory) copied into `stage` on
+// ctx->stream
+static int device_view(zkmi_ctx* ctx, const void* src, size_t bytes, void* stage, const void** out) {
+  *out = src;
+  if (pointer_kind(src) == PTR_DEVICE) return ZKMI_OK;
+  ZK_HIP(hipMemcpyAsync(stage, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  *out = stage;
+  return ZKMI_OK;
+}
+
+int prove_set_begin(zkmi_ctx* ctx, const zkmi_pk* pk, size_t value_rows, size_t n_staged,
+                    size_t batch, const void* rs, hipStream_t* main, char** stage) {
+  zkmi_ctx::ProveSet& S = ctx->sets[ctx->next_submit];
+  if (S.pending) {
+    ctx->err = "prove: two batches already in flight; collect one first";
+    return ZKMI_ERR_ARG;
+  }
+  const size_t Bp = round_up(batch, 64);
+  const SetBytes sb = prove_set_bytes(value_rows, (size_t)1 << pk->log_n, n_staged, batch, Bp);
+  // Size the other set too, so that steady-state submits never allocate -- but only while that
+  // set is idle: a pending set keeps raw pointers into its buffers (S.rs, S.commit_pts, ...), and
+  // its solve / quotient / MSM kernels may be running on them.  A pending set is resized by its
+  // own next submit, after its collect.
+  int rc;
+  for (zkmi_ctx::ProveSet* T : {&ctx->sets[ctx->next_submit ^ 1], &S}) {
+    if (T->pending) continue;
+    if ((rc = ensure_scratch(ctx, T->slots, sb.slots)) || (rc = ensure_scratch(ctx, T->a, sb.abc)) ||
+        (rc = ensure_scratch(ctx, T->b, sb.abc)) || (rc = ensure_scratch(ctx, T->c, sb.abc)) ||
+        (rc = ensure_scratch(ctx, T->misc, sb.misc)) ||
+        (rc = ensure_scratch(ctx, T->sums, sums_bytes(Bp))))
+      return rc;
+  }
+  char* const staged = (char*)S.misc.p + Bp * 100;
+  S.rs = S.misc.p;
+  S.st = (char*)S.misc.p + Bp * 96;
+  if (stage) *stage = staged;
+  S.heavy_enqueued = false;
+  S.batch = batch;
+  S.Bp = Bp;
+  S.pk = pk;
+  *main = ctx->stream;
+  ctx->stream = ctx->stream2;   // the helpers launch on ctx->stream
+  hipEventRecord(S.ev0, ctx->stream);
+  const void* rs_dev;
+  rc = device_view(ctx, rs, batch * 64, staged + batch * n_staged * 32, &rs_dev);
+  if (!rc) rc = transpose_in(ctx, rs_dev, S.rs, 2, batch, Bp, 32);
+  return rc ? prove_set_end(ctx, *main, rc) : ZKMI_OK;
+}
+
+int prove_set_end(zkmi_ctx* ctx, hipStream_t main, int rc) {
+  zkmi_ctx::ProveSet& S = ctx->sets[ctx->next_submit];
+  hipEventRecord(S.ev1, ctx->stream);
+  ctx->stream = main;
+  if (rc) {
+    hipStreamSynchronize(ctx->stream2);   // nothing of a failed submit stays queued on caller memory
+    return rc;
+  }
+  S.pending = true;
+  ctx->next_submit ^= 1;
+  return ZKMI_OK;
+}
+
 }  // namespace zk
 
 // ===================================================================================================
@@ -298,8 +397,12 @@ void zkmi_destroy(zkmi_ctx* ctx) {
     hipFree(p.coset29_fwd);
     hipFree(p.coset29n_fwd);
   }
-  for (auto& s : ctx->scratch)
-    if (s.p) hipFree(s.p);
+  for (auto& st : ctx->sets)
+    for (DevBuf* b : {&st.slots, &st.a, &st.b, &st.c, &st.misc, &st.sums, &st.commit})
+      if (b->p) hipFree(b->p);
+  for (DevBuf* b : {&ctx->ntt_tmp, &ctx->build_tmp, &ctx->msm_digits, &ctx->msm_sint,
+                    &ctx->msm_part[0], &ctx->msm_part[1], &ctx->side_part2, &ctx->side_part3})
+    if (b->p) hipFree(b->p);
   witness_ring_free(ctx);
   for (auto& e : ctx->ev)
     if (e) hipEventDestroy(e);
@@ -342,14 +445,11 @@ int zkmi_field_mul(zkmi_ctx* ctx, int which, const void* a, const void* b, void*
 
 int zkmi_field_mul_bench(zkmi_ctx* ctx, int which, size_t n_threads, int iters, double* rate) {
   ZK_HIP(hipSetDevice(ctx->device));
-  if (ctx->sets[0].pending || ctx->sets[1].pending) {
-    ctx->err = "a submitted prove batch is in flight; collect it first";
-    return ZKMI_ERR_ARG;
-  }
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
   n_threads = round_up(n_threads, 256);
   void* buf;
-  int rc = ensure_scratch(ctx, 5, n_threads * 32, &buf);
-  if (rc) return rc;
+  if ((rc = ensure_scratch(ctx, ctx->sets[0].misc, n_threads * 32, &buf))) return rc;
   // every byte 0x11: top limb 0x11111111 < 0x30644e72, so the element is < p
   ZK_HIP(hipMemsetAsync(buf, 0x11, n_threads * 32, ctx->stream));
   auto launch = [&]() {
@@ -376,20 +476,17 @@ int zkmi_field_mul_bench(zkmi_ctx* ctx, int which, size_t n_threads, int iters, 
 
 int zkmi_ntt_batch(zkmi_ctx* ctx, void* data, int log_n, size_t batch, int inverse, int coset) {
   ZK_HIP(hipSetDevice(ctx->device));
-  if (ctx->sets[0].pending || ctx->sets[1].pending) {
-    ctx->err = "a submitted prove batch is in flight; collect it first";
-    return ZKMI_ERR_ARG;
-  }
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
   if (batch == 0) return ZKMI_OK;
   NttPlan* plan;
-  int rc = get_plan(ctx, log_n, &plan);
-  if (rc) return rc;
+  if ((rc = get_plan(ctx, log_n, &plan))) return rc;
   const size_t n = (size_t)1 << log_n, Bp = round_up(batch, 64);
   Staged sd(ctx), so(ctx);
   if ((rc = sd.in(data, batch * n * 32)) || (rc = so.out(data, batch * n * 32))) return rc;
   void *t0, *t1;
-  if ((rc = ensure_scratch(ctx, 1, n * Bp * 32, &t0)) ||
-      (rc = ensure_scratch(ctx, 2, n * Bp * 32, &t1)))
+  if ((rc = ensure_scratch(ctx, ctx->sets[0].a, n * Bp * 32, &t0)) ||
+      (rc = ensure_scratch(ctx, ctx->sets[0].b, n * Bp * 32, &t1)))
     return rc;
   if ((rc = transpose_in(ctx, sd.dev, t0, n, batch, Bp, 32))) return rc;
   if ((rc = ntt_bi(ctx, plan, (const Fr*)t0, (Fr*)t1, Bp, inverse != 0, coset != 0, n))) return rc;
@@ -402,22 +499,20 @@ int zkmi_ntt_batch(zkmi_ctx* ctx, void* data, int log_n, size_t batch, int inver
 int zkmi_h_batch(zkmi_ctx* ctx, const void* a, const void* b, const void* c, void* h_out,
                  int log_n, size_t batch) {
   ZK_HIP(hipSetDevice(ctx->device));
-  if (ctx->sets[0].pending || ctx->sets[1].pending) {
-    ctx->err = "a submitted prove batch is in flight; collect it first";
-    return ZKMI_ERR_ARG;
-  }
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
   if (batch == 0) return ZKMI_OK;
   NttPlan* plan;
-  int rc = get_plan(ctx, log_n, &plan);
-  if (rc) return rc;
+  if ((rc = get_plan(ctx, log_n, &plan))) return rc;
   const size_t n = (size_t)1 << log_n, Bp = round_up(batch, 64);
   Staged sa(ctx), sb(ctx), sc(ctx), sh(ctx);
   if ((rc = sa.in(a, batch * n * 32)) || (rc = sb.in(b, batch * n * 32)) ||
       (rc = sc.in(c, batch * n * 32)) || (rc = sh.out(h_out, batch * n * 32)))
     return rc;
   void* t[4];
+  DevBuf* tb[4] = {&ctx->sets[0].a, &ctx->sets[0].b, &ctx->sets[0].c, &ctx->ntt_tmp};
   for (int i = 0; i < 4; i++)
-    if ((rc = ensure_scratch(ctx, 1 + i, n * Bp * 32, &t[i]))) return rc;
+    if ((rc = ensure_scratch(ctx, *tb[i], n * Bp * 32, &t[i]))) return rc;
   if ((rc = transpose_in(ctx, sa.dev, t[0], n, batch, Bp, 32)) ||
       (rc = transpose_in(ctx, sb.dev, t[1], n, batch, Bp, 32)) ||
       (rc = transpose_in(ctx, sc.dev, t[2], n, batch, Bp, 32)))
@@ -468,22 +563,23 @@ static WinPlan plan_explicit(int wb) {
 }
 static const int COMB_WINDOWS = 254;
 // HBM the prover needs beside the tables to prove batches of up to `max_batch` with a key of this
-// shape: two pipeline sets of {value file, a, b, c, staged inputs}, the NTT scratch,
-// the MSM integer scalars + digits + two partial-sum buffers, the per-set sums, the table-build
-// scratch that stays allocated, and a margin for the allocator.
+// shape: two pipeline sets (value file, a, b, c, staged inputs, sums, commitment
+// buffers), the NTT scratch, the MSM integer scalars + digits + two partial-sum buffers, the
+// table-build scratch that stays allocated, and a margin for the allocator.
 static double prove_working_set_bytes(uint32_t log_n, size_t n_slots, size_t n_in, size_t max_batch,
-                                      size_t n_msm_max) {
-  const double Bp = (double)round_up(max_batch ? max_batch : 1024, 64);
-  const double n = (double)((size_t)1 << log_n);
-  const double set = (double)n_slots * Bp * 32 + 3 * n * Bp * 32 + Bp * 100 + Bp * (n_in * 32 + 64);
+                                      size_t n_msm_max, size_t n_commitments) {
+  const size_t Bp = round_up(max_batch ? max_batch : 1024, 64);
+  const size_t n = (size_t)1 << log_n;
+  const SetBytes sb = prove_set_bytes(n_slots, n, n_in, Bp, Bp);
+  const double set = (double)(sb.slots + 3 * sb.abc + sb.misc + sums_bytes(Bp) +
+                              commit_buffer_bytes(n_commitments, Bp));
   const double digits = 254.0 * (double)((n_msm_max + 15) / 16) * Bp * 4;   // comb, k >= 16
   const double sint = (double)n_msm_max * Bp * 32;
   const double partials = 2 * 21.0 * 254 * Bp * 256;
-  const double sums = 2 * Bp * (7 * 128 + 2 * 256 + 256 + 256.0 * (4 * 128 + 256));
   // device half of the witness entry's staging ring (witness.hip): three chunks of ~64 MB, or of
   // one 64-proof column block of the wire matrix when that is larger (n_in = n_wires here)
   const double ring = 3.0 * std::max(68e6, (double)n_in * 32 * 64);
-  return 2 * set + n * Bp * 32 + digits + sint + partials + sums + ring + 2e9 + 1e9;
+  return 2 * set + (double)n * Bp * 32 + digits + sint + partials + ring + 2e9 + 1e9;
 }
 static double free_hbm_bytes() {
   size_t free_b = 0, total_b = 0;
@@ -546,20 +642,17 @@ void zkmi_msm_bases_free(zkmi_ctx* ctx, zkmi_msm_bases* b) {
 int zkmi_msm_batch(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const void* scalars, size_t batch,
                    void* out) {
   ZK_HIP(hipSetDevice(ctx->device));
-  if (ctx->sets[0].pending || ctx->sets[1].pending) {
-    ctx->err = "a submitted prove batch is in flight; collect it first";
-    return ZKMI_ERR_ARG;
-  }
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
   if (batch == 0) return ZKMI_OK;
   const size_t n = bases->n, Bp = round_up(batch, 64);
   const size_t pt = bases->group == 1 ? 64 : 128;
   Staged ss(ctx), so(ctx);
-  int rc;
   if ((rc = ss.in(scalars, batch * n * 32)) || (rc = so.out(out, batch * pt))) return rc;
   void *sbi, *acc, *aff;
-  if ((rc = ensure_scratch(ctx, 1, (n ? n : 1) * Bp * 32, &sbi)) ||
-      (rc = ensure_scratch(ctx, 2, Bp * pt * 2, &acc)) ||
-      (rc = ensure_scratch(ctx, 3, Bp * pt, &aff)))
+  if ((rc = ensure_scratch(ctx, ctx->sets[0].a, (n ? n : 1) * Bp * 32, &sbi)) ||
+      (rc = ensure_scratch(ctx, ctx->sets[0].b, Bp * pt * 2, &acc)) ||
+      (rc = ensure_scratch(ctx, ctx->sets[0].c, Bp * pt, &aff)))
     return rc;
   if ((rc = transpose_in(ctx, ss.dev, sbi, n, batch, Bp, 32))) return rc;
   if ((rc = msm_run(ctx, bases, (const Fr*)sbi, nullptr, Bp, acc))) return rc;
@@ -574,22 +667,19 @@ int zkmi_fixed_base_mul(zkmi_ctx* ctx, int group, const void* base, const void* 
                         void* out) {
   // an MSM over ONE base with the scalars playing the role of the batch
   ZK_HIP(hipSetDevice(ctx->device));
-  if (ctx->sets[0].pending || ctx->sets[1].pending) {
-    ctx->err = "a submitted prove batch is in flight; collect it first";
-    return ZKMI_ERR_ARG;
-  }
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
   if (n == 0) return ZKMI_OK;
   zkmi_msm_bases* b = nullptr;
-  int rc = zkmi_msm_bases_load(ctx, group, base, 1, 8, &b);
-  if (rc) return rc;
+  if ((rc = zkmi_msm_bases_load(ctx, group, base, 1, 8, &b))) return rc;
   const size_t Bp = round_up(n, 64);
   const size_t pt = group == 1 ? 64 : 128;
   Staged ss(ctx), so(ctx);
   void *sbi = nullptr, *acc = nullptr, *aff = nullptr;
   if ((rc = ss.in(scalars, n * 32)) || (rc = so.out(out, n * pt)) ||
-      (rc = ensure_scratch(ctx, 1, Bp * 32, &sbi)) ||
-      (rc = ensure_scratch(ctx, 2, Bp * pt * 2, &acc)) ||
-      (rc = ensure_scratch(ctx, 3, Bp * pt, &aff))) {
+      (rc = ensure_scratch(ctx, ctx->sets[0].a, Bp * 32, &sbi)) ||
+      (rc = ensure_scratch(ctx, ctx->sets[0].b, Bp * pt * 2, &acc)) ||
+      (rc = ensure_scratch(ctx, ctx->sets[0].c, Bp * pt, &aff))) {
     zkmi_msm_bases_free(ctx, b);
     return rc;
   }
@@ -762,7 +852,8 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
   const size_t n_msm_max = std::max(std::max((size_t)d->n_a, (size_t)d->n_b),
                                     std::max((size_t)d->n_k, (size_t)n_z));
   const size_t n_slots = d->n_slots_hint ? d->n_slots_hint : (size_t)d->n_wires + d->n_wires / 20;
-  const double ws = prove_working_set_bytes(d->log_n, n_slots, d->n_wires, pk->max_batch, n_msm_max);
+  const double ws = prove_working_set_bytes(d->log_n, n_slots, d->n_wires, pk->max_batch, n_msm_max,
+                                            pk->commits.size());
   double usable = free_hbm_bytes() - ws;
   if (usable < 0) usable = 0;
   if (d->table_budget_bytes && (double)d->table_budget_bytes < usable)
@@ -1094,10 +1185,8 @@ static int stage_inputs(zkmi_ctx* ctx, const zkmi_cs* cs, const void* inputs_dev
 int zkmi_solve_batch(zkmi_ctx* ctx, const zkmi_cs* cs, const void* inputs, size_t batch,
                      void* wires_out, void* abc_out, int32_t* status_out) {
   ZK_HIP(hipSetDevice(ctx->device));
-  if (ctx->sets[0].pending || ctx->sets[1].pending) {
-    ctx->err = "a submitted prove batch is in flight; collect it first";
-    return ZKMI_ERR_ARG;
-  }
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
   if (batch == 0) return ZKMI_OK;
   if (!cs->commit_rows.empty()) {
     ctx->err = "solve_batch: this system has commitments; its commitment wires come from the "
@@ -1108,17 +1197,17 @@ int zkmi_solve_batch(zkmi_ctx* ctx, const zkmi_cs* cs, const void* inputs, size_
   const size_t n_in = cs->n_public - 1 + cs->n_secret;
   const size_t nc = cs->n_constraints ? cs->n_constraints : 1;
   Staged si(ctx), sw(ctx), sabc(ctx), sst(ctx);
-  int rc;
   if ((rc = si.in(inputs, batch * n_in * 32))) return rc;
   if (wires_out && (rc = sw.out(wires_out, batch * (size_t)cs->n_wires * 32))) return rc;
   if (abc_out && (rc = sabc.out(abc_out, 3 * batch * (size_t)cs->n_constraints * 32))) return rc;
   if ((rc = sst.out(status_out, batch * 4))) return rc;
   void *slots, *a, *b, *c, *st;
-  if ((rc = ensure_scratch(ctx, 0, (size_t)cs->n_slots * Bp * 32, &slots)) ||
-      (rc = ensure_scratch(ctx, 1, nc * Bp * 32, &a)) ||
-      (rc = ensure_scratch(ctx, 2, nc * Bp * 32, &b)) ||
-      (rc = ensure_scratch(ctx, 3, nc * Bp * 32, &c)) ||
-      (rc = ensure_scratch(ctx, 5, Bp * 4, &st)))
+  zkmi_ctx::ProveSet& S = ctx->sets[0];
+  if ((rc = ensure_scratch(ctx, S.slots, (size_t)cs->n_slots * Bp * 32, &slots)) ||
+      (rc = ensure_scratch(ctx, S.a, nc * Bp * 32, &a)) ||
+      (rc = ensure_scratch(ctx, S.b, nc * Bp * 32, &b)) ||
+      (rc = ensure_scratch(ctx, S.c, nc * Bp * 32, &c)) ||
+      (rc = ensure_scratch(ctx, S.misc, Bp * 4, &st)))
     return rc;
   if ((rc = stage_inputs(ctx, cs, si.dev, batch, Bp, (Fr*)slots))) return rc;
   if ((rc = solve_bi(ctx, cs, (Fr*)slots, (Fr*)a, (Fr*)b, (Fr*)c, (int32_t*)st, Bp))) return rc;
@@ -1143,8 +1232,6 @@ int zkmi_solve_batch(zkmi_ctx* ctx, const zkmi_cs* cs, const void* inputs, size_
   ZK_HIP(hipStreamSynchronize(ctx->stream));
   return ZKMI_OK;
 }
-
-static bool any_pending(zkmi_ctx* ctx) { return ctx->sets[0].pending || ctx->sets[1].pending; }
 
 // Stage 1 of a prove: inputs -> value file, witness solve.  Runs on stream2 so that it overlaps
 // the NTT/MSM kernels of the previously submitted batch (the solve is a 16-wavefront latency chain).
@@ -1174,125 +1261,42 @@ int zkmi_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_cs* cs, const
                  "constraint system and in the proving key";
       return ZKMI_ERR_ARG;
     }
-  const int si = ctx->next_submit;
-  zkmi_ctx::ProveSet& S = ctx->sets[si];
-  if (S.pending) {
-    ctx->err = "prove: two batches already in flight; collect one first";
-    return ZKMI_ERR_ARG;
-  }
-  const size_t Bp = round_up(batch, 64);
-  const size_t n = (size_t)1 << pk->log_n;
   const size_t n_in = cs->n_public - 1 + cs->n_secret;
-  int rc;
-  const int base = si == 0 ? 0 : 8;   // scratch slots 0-3,5 (set 0) / 8-11,13 (set 1)
-  void* misc;
-  // Size the other set too, so that steady-state submits never allocate -- but only while that
-  // set is idle: a pending set keeps raw pointers into its buffers (S.slots, S.a, ...), and its
-  // solve / quotient / MSM kernels may be running on them.  A pending set is resized by its own
-  // next submit, after its collect.
-  if (!ctx->sets[si ^ 1].pending) {
-    void* dummy;
-    const int ob = si == 0 ? 8 : 0;
-    if ((rc = ensure_scratch(ctx, ob + 0, (size_t)cs->n_slots * Bp * 32, &dummy)) ||
-        (rc = ensure_scratch(ctx, ob + 1, n * Bp * 32, &dummy)) ||
-        (rc = ensure_scratch(ctx, ob + 2, n * Bp * 32, &dummy)) ||
-        (rc = ensure_scratch(ctx, ob + 3, n * Bp * 32, &dummy)) ||
-        (rc = ensure_scratch(ctx, ob + 5, Bp * (96 + 4) + batch * (n_in * 32 + 64), &dummy)) ||
-        (rc = ensure_scratch(ctx, si == 0 ? 15 : 14, Bp * (7 * 128 + 2 * 256 + 256), &dummy)))
-      return rc;
-  }
-  if ((rc = ensure_scratch(ctx, si == 0 ? 14 : 15, Bp * (7 * 128 + 2 * 256 + 256 + 256 * (4 * 128 + 256)),
-                           &S.sums)))
-    return rc;
-  S.heavy_enqueued = false;
-  if ((rc = ensure_scratch(ctx, base + 0, (size_t)cs->n_slots * Bp * 32, &S.slots)) ||
-      (rc = ensure_scratch(ctx, base + 1, n * Bp * 32, &S.a)) ||
-      (rc = ensure_scratch(ctx, base + 2, n * Bp * 32, &S.b)) ||
-      (rc = ensure_scratch(ctx, base + 3, n * Bp * 32, &S.c)) ||
-      (rc = ensure_scratch(ctx, base + 5, Bp * (96 + 4) + batch * (n_in * 32 + 64), &misc)))
-    return rc;
-  S.rs = misc;
-  S.st = (char*)misc + Bp * 96;
-  char* stage_in = (char*)misc + Bp * 100;
-  char* stage_rs = stage_in + batch * n_in * 32;
-  hipStream_t q = ctx->stream2;
-  // caller buffers are consumed before this function returns only if they are host memory
-  // (pageable copies are synchronous); device buffers must stay valid until the collect
-  const void* in_dev = inputs;
-  const void* rs_dev = rs;
-  if (!is_device_ptr(inputs)) {
-    ZK_HIP(hipMemcpyAsync(stage_in, inputs, batch * n_in * 32, hipMemcpyHostToDevice, q));
-    in_dev = stage_in;
-  }
-  if (!is_device_ptr(rs)) {
-    ZK_HIP(hipMemcpyAsync(stage_rs, rs, batch * 64, hipMemcpyHostToDevice, q));
-    rs_dev = stage_rs;
-  }
-  hipStream_t saved = ctx->stream;
-  ctx->stream = q;  // the helpers launch on ctx->stream
-  hipEventRecord(S.ev0, q);
-  rc = transpose_in(ctx, in_dev, (Fr*)S.slots + Bp, n_in, batch, Bp, 32);
-  if (!rc) rc = rows_to_f_domain(ctx, (Fr*)S.slots + Bp, n_in, Bp);
-  if (!rc) rc = transpose_in(ctx, rs_dev, S.rs, 2, batch, Bp, 32);
-  S.batch = batch;
-  S.Bp = Bp;
-  S.pk = pk;
+  hipStream_t main;
+  char* stage;
+  int rc = prove_set_begin(ctx, pk, cs->n_slots, n_in, batch, rs, &main, &stage);
+  if (rc) return rc;
+  zkmi_ctx::ProveSet& S = ctx->sets[ctx->next_submit];
+  const size_t Bp = S.Bp;
   S.cs = cs;
   S.n_constraints = cs->n_constraints;
   S.f_domain = true;
+  Fr *slots = (Fr*)S.slots.p, *a = (Fr*)S.a.p, *b = (Fr*)S.b.p, *c = (Fr*)S.c.p;
+  int32_t* st = (int32_t*)S.st;
+  // caller buffers are consumed before this function returns only if they are host memory
+  // (pageable copies are synchronous); device buffers must stay valid until the collect
+  const void* in_dev;
+  rc = device_view(ctx, inputs, batch * n_in * 32, stage, &in_dev);
+  if (!rc) rc = stage_inputs(ctx, cs, in_dev, batch, Bp, slots);
   if (!rc && cs->commit_rows.empty()) {
-    rc = solve_bi(ctx, cs, (Fr*)S.slots, (Fr*)S.a, (Fr*)S.b, (Fr*)S.c, (int32_t*)S.st, Bp);
+    rc = solve_bi(ctx, cs, slots, a, b, c, st, Bp);
   } else if (!rc) {
     // commitment extension: the program stops at every COMMIT row; the commitment is an MSM over
     // the wires solved so far, its hash becomes the commitment wire's value (commit.hip: the
     // host blocks on this stream for the hash -- the main stream keeps running the previous
     // batch's MSMs meanwhile)
-    rc = solve_init(ctx, (Fr*)S.slots, (int32_t*)S.st, Bp);
+    rc = solve_init(ctx, slots, st, Bp);
     uint32_t begin = 0;
     for (size_t i = 0; !rc && i < cs->commit_rows.size(); i++) {
-      rc = solve_rows(ctx, cs, (Fr*)S.slots, (Fr*)S.a, (Fr*)S.b, (Fr*)S.c, (int32_t*)S.st, Bp, begin,
-                      cs->commit_rows[i].first);
+      rc = solve_rows(ctx, cs, slots, a, b, c, st, Bp, begin, cs->commit_rows[i].first);
       if (!rc) rc = commit_phase(ctx, S, (uint32_t)i, true);
       begin = cs->commit_rows[i].first + 1;
     }
-    if (!rc)
-      rc = solve_rows(ctx, cs, (Fr*)S.slots, (Fr*)S.a, (Fr*)S.b, (Fr*)S.c, (int32_t*)S.st, Bp, begin,
-                      cs->n_rows);
+    if (!rc) rc = solve_rows(ctx, cs, slots, a, b, c, st, Bp, begin, cs->n_rows);
     if (!rc) rc = commit_finish_submit(ctx, S);
   }
-  hipEventRecord(S.ev1, q);
-  ctx->stream = saved;
-  if (rc) return rc;
-  S.pending = true;
-  ctx->next_submit ^= 1;
-  return ZKMI_OK;
+  return prove_set_end(ctx, main, rc);
 }
-
-struct SumsView {
-  G1XYZZ *sA, *sB1, *sK, *sZ, *tR, *tS, *tNRS;
-  G2XYZZ *sB2, *tS2;
-  ProofOut* proofs;
-  G1XYZZ* w1[4];   // deferred window sums of A, B1, K, Z ([<= 256][Bp] each)
-  G2XYZZ* w2;
-  SumsView(void* base, size_t Bp) {
-    char* m = (char*)base;
-    sA = (G1XYZZ*)m;   m += Bp * 128;
-    sB1 = (G1XYZZ*)m;  m += Bp * 128;
-    sK = (G1XYZZ*)m;   m += Bp * 128;
-    sZ = (G1XYZZ*)m;   m += Bp * 128;
-    tR = (G1XYZZ*)m;   m += Bp * 128;
-    tS = (G1XYZZ*)m;   m += Bp * 128;
-    tNRS = (G1XYZZ*)m; m += Bp * 128;
-    sB2 = (G2XYZZ*)m;  m += Bp * 256;
-    tS2 = (G2XYZZ*)m;  m += Bp * 256;
-    proofs = (ProofOut*)m;  m += Bp * 256;
-    for (int i = 0; i < 4; i++) {
-      w1[i] = (G1XYZZ*)m;
-      m += 256 * Bp * 128;
-    }
-    w2 = (G2XYZZ*)m;
-  }
-};
 
 // The ALU-heavy part of stage 2 (quotient, five MSMs, the one-base delta MSMs) of set `si`, on the
 // main stream.  Everything it touches besides the set's own buffers (NTT scratch, MSM partials) is
@@ -1306,15 +1310,15 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
   int rc = get_plan(ctx, (int)pk->log_n, &plan);
   if (rc) return rc;
   void* t0;
-  if ((rc = ensure_scratch(ctx, 4, n * Bp * 32, &t0))) return rc;
-  SumsView v(S.sums, Bp);
+  if ((rc = ensure_scratch(ctx, ctx->ntt_tmp, n * Bp * 32, &t0))) return rc;
+  SumsView v(S.sums.p, Bp);
   Fr* rs_bi = (Fr*)S.rs;
-  Fr* slots = (Fr*)S.slots;
+  Fr* slots = (Fr*)S.slots.p;
   ZK_HIP(hipStreamWaitEvent(ctx->stream, S.ev1, 0));
   hipEventRecord(S.evq[0], ctx->stream);
   Fr* h;
-  if ((rc = compute_h_bi(ctx, plan, (Fr*)S.a, (Fr*)S.b, (Fr*)S.c, (Fr*)t0, Bp, S.n_constraints,
-                         &h, fd)))
+  if ((rc = compute_h_bi(ctx, plan, (Fr*)S.a.p, (Fr*)S.b.p, (Fr*)S.c.p, (Fr*)t0, Bp,
+                         S.n_constraints, &h, fd)))
     return rc;
   hipEventRecord(S.evq[1], ctx->stream);
   S.msm_ev_used = 0;
@@ -1382,7 +1386,7 @@ int zkmi_prove_collect_ex(zkmi_ctx* ctx, void* proofs_out, int32_t* status_out,
   const size_t batch = S.batch, Bp = S.Bp;
   int rc;
   if (!S.heavy_enqueued && (rc = enqueue_heavy(ctx, si))) return rc;
-  SumsView v(S.sums, Bp);
+  SumsView v(S.sums.p, Bp);
   hipStream_t q3 = ctx->stream3;
   ZK_HIP(hipStreamWaitEvent(q3, S.evq[4], 0));
   hipEventRecord(S.eva[0], q3);
@@ -1457,12 +1461,8 @@ int zkmi_prove_collect_ex(zkmi_ctx* ctx, void* proofs_out, int32_t* status_out,
 int zkmi_prove_batch(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_cs* cs, const void* inputs,
                      size_t batch, const void* rs, void* proofs_out, int32_t* status_out) {
   if (batch == 0) return ZKMI_OK;
-  if (any_pending(ctx)) {
-    ctx->err = "prove_batch: batches submitted with zkmi_prove_submit are still in flight";
-    return ZKMI_ERR_ARG;
-  }
-  int rc = zkmi_prove_submit(ctx, pk, cs, inputs, batch, rs);
-  if (rc) return rc;
+  int rc;
+  if ((rc = require_idle(ctx)) || (rc = zkmi_prove_submit(ctx, pk, cs, inputs, batch, rs))) return rc;
   return zkmi_prove_collect(ctx, proofs_out, status_out);
 }
 

@@ -212,13 +212,14 @@ int commit_keys_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk* pk) {
 }
 
 // buffers of a set for a key with commitments: points (n x Bp affine), folding powers (n rows),
-// proof of knowledge (Bp XYZZ + Bp affine)
-static int commit_buffers(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S, int si) {
+// proof of knowledge (Bp XYZZ + Bp affine), accumulator (Bp XYZZ)
+size_t commit_buffer_bytes(size_t n, size_t Bp) {
+  return n ? n * Bp * 64 + n * Bp * 32 + Bp * (128 + 64) + Bp * 128 : 0;
+}
+static int commit_buffers(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S) {
   const size_t n = S.pk->commits.size(), Bp = S.Bp;
   void* base;
-  // scratch slots 19 (set 0) / 20 (set 1): owned by the set, like its value file
-  int rc = ensure_scratch(ctx, si == 0 ? 19 : 20, n * Bp * 64 + n * Bp * 32 + Bp * (128 + 64) + Bp * 128,
-                          &base);
+  int rc = ensure_scratch(ctx, S.commit, commit_buffer_bytes(n, Bp), &base);
   if (rc) return rc;
   S.commit_pts = base;
   S.commit_ch = (char*)base + n * Bp * 64;
@@ -233,7 +234,7 @@ int commit_phase(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S, uint32_t index, bool writ
   const zkmi_commit_key& ck = pk->commits[index];
   int rc;
   if (index == 0) {
-    if ((rc = commit_buffers(ctx, S, (int)(&S - ctx->sets)))) return rc;
+    if ((rc = commit_buffers(ctx, S))) return rc;
     S.commit_host.assign(n * batch, Fr::zero());
   }
   // D = <w[private], Basis>: the value file's wire rows are the scalars
@@ -241,7 +242,7 @@ int commit_phase(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S, uint32_t index, bool writ
   G1Affine* pts = (G1Affine*)S.commit_pts + index * Bp;
   if (ck.n_private == 0) {   // nothing private committed: the commitment is the point at infinity
     ZK_HIP(hipMemsetAsync(pts, 0, Bp * 64, ctx->stream));
-  } else if ((rc = msm_run(ctx, ck.basis, (const Fr*)S.slots, ck.private_dev, Bp, acc, S.f_domain)) ||
+  } else if ((rc = msm_run(ctx, ck.basis, (const Fr*)S.slots.p, ck.private_dev, Bp, acc, S.f_domain)) ||
              (rc = xyzz_to_affine(ctx, 1, acc, pts, Bp))) {
     return rc;
   }
@@ -250,7 +251,7 @@ int commit_phase(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S, uint32_t index, bool writ
   // wires' values.  Witness path: the caller's solver already did that; read the wire back.
   std::vector<uint4> row(2 * Bp);
   const size_t row_bytes = 2 * Bp * 16;
-  auto row_ptr = [&](uint32_t w) { return (const char*)S.slots + (size_t)w * row_bytes; };
+  auto row_ptr = [&](uint32_t w) { return (const char*)S.slots.p + (size_t)w * row_bytes; };
   Fr* host = S.commit_host.data() + (size_t)index * batch;   // plain integers
   if (!write_wire) {
     ZK_HIP(hipMemcpyAsync(row.data(), row_ptr(ck.wire), row_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -322,12 +323,12 @@ int commit_pok(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S) {
   G1Affine* pok_aff = (G1Affine*)((char*)S.commit_pok + Bp * 128);
   if (n == 1 && pk->commits[0].n_private) {
     const zkmi_commit_key& ck = pk->commits[0];
-    if ((rc = msm_run(ctx, ck.sigma, (const Fr*)S.slots, ck.private_dev, Bp, pok, S.f_domain))) return rc;
+    if ((rc = msm_run(ctx, ck.sigma, (const Fr*)S.slots.p, ck.private_dev, Bp, pok, S.f_domain))) return rc;
   } else {
     size_t mx = 1;
     for (auto& ck : pk->commits) mx = std::max<size_t>(mx, ck.n_private);
     void *tmp, *part;
-    if ((rc = ensure_scratch(ctx, 7, mx * Bp * 32 + Bp * 128, &tmp))) return rc;
+    if ((rc = ensure_scratch(ctx, ctx->build_tmp, mx * Bp * 32 + Bp * 128, &tmp))) return rc;
     part = (char*)tmp + mx * Bp * 32;
     for (size_t i = 0; i < n; i++) {
       const zkmi_commit_key& ck = pk->commits[i];
@@ -340,7 +341,7 @@ int commit_pok(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S) {
         continue;
       }
       hipLaunchKernelGGL(pok_scale_kernel, dim3((unsigned)((Bp + 255) / 256), (unsigned)std::min<uint32_t>(ck.n_private, 1024)),
-                           dim3(256), 0, ctx->stream, (const Fr*)S.slots, ck.private_dev,
+                           dim3(256), 0, ctx->stream, (const Fr*)S.slots.p, ck.private_dev,
                            (const Fr*)((char*)S.commit_ch + i * Bp * 32), (Fr*)tmp, ck.n_private, Bp,
                            S.f_domain ? 1 : 0);
       if ((rc = msm_run(ctx, ck.sigma, (const Fr*)tmp, nullptr, Bp, part, S.f_domain))) return rc;

@@ -863,7 +863,7 @@ int build_comb(zkmi_ctx* ctx, const Affine<F>* bases_dev, size_t n, const WinPla
   void* scratch;
   const size_t dp_bytes = round_up(n_groups * k * sizeof(Affine<F>), 256);
   const size_t gs_bytes = round_up((n_groups + 1) * sizeof(Affine<F>), 256);
-  int rc = ensure_scratch(ctx, 7, dp_bytes + gs_bytes + 256 + per_thread * T, &scratch);
+  int rc = ensure_scratch(ctx, ctx->build_tmp, dp_bytes + gs_bytes + 256 + per_thread * T, &scratch);
   if (rc) return rc;
   Affine<F>* dpts = (Affine<F>*)scratch;
   Affine<F>* gsum = (Affine<F>*)((char*)scratch + dp_bytes);
@@ -906,7 +906,7 @@ int build_impl(zkmi_ctx* ctx, const Affine<F>* bases_dev, size_t n, const WinPla
   T = round_up(T, 64);
   if (T > 262144) T = 262144;
   void* scratch;
-  int rc = ensure_scratch(ctx, 7, per_thread * T, &scratch);
+  int rc = ensure_scratch(ctx, ctx->build_tmp, per_thread * T, &scratch);
   if (rc) return rc;
   for (uint64_t r0 = 0; r0 < n_rows; r0 += T) {
     hipLaunchKernelGGL((msm_build_table<F>), dim3((unsigned)(T / 64)), dim3(64), 0, ctx->stream,
@@ -1018,7 +1018,7 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
     // writes the other partial buffer
     const bool defer = wsum_out && finish_stream && finish_stream != ctx->stream;
     const int pb = defer ? (int)(ctx->part_next++ & 1u) : 0;
-    int rc = ensure_scratch(ctx, pb ? 16 : 6,
+    int rc = ensure_scratch(ctx, ctx->msm_part[pb],
                             ((chunks + ngroups + 1) * W) * Bp * sizeof(XYZZ<F>), &partial);
     if (rc) return rc;
     if (ctx->part_ev_valid[pb]) {   // the last reduction that read this buffer must be done
@@ -1028,8 +1028,8 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
     // (Measured and dropped: the digit pass one MSM ahead on a fourth stream through two digit
     // buffers -- correct, no gain: the pass is ALU work like the accumulate kernel it would hide
     // under, which slowed down by exactly the pass's 7 ms.)
-    if ((rc = ensure_scratch(ctx, 12, (size_t)W * G * Bp * sizeof(uint32_t), &digits))) return rc;
-    if ((rc = ensure_scratch(ctx, 17, n * Bp * sizeof(Fr), &sint))) return rc;
+    if ((rc = ensure_scratch(ctx, ctx->msm_digits, (size_t)W * G * Bp * sizeof(uint32_t), &digits))) return rc;
+    if ((rc = ensure_scratch(ctx, ctx->msm_sint, n * Bp * sizeof(Fr), &sint))) return rc;
     hipStream_t dq = ctx->stream;
     XYZZ<F>* mid = (XYZZ<F>*)partial + chunks * W * Bp;
     XYZZ<F>* wsum = wsum_out ? wsum_out : mid + (size_t)ngroups * W * Bp;
@@ -1122,13 +1122,13 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
     while ((size_t)group * group < chunks) group++;
     const uint32_t ngroups = (uint32_t)((chunks + group - 1) / group);
     void *partial, *digits;
-    int rc = ensure_scratch(ctx, 6, ((chunks + ngroups + 1) * W) * Bp * sizeof(XYZZ<F>), &partial);
+    int rc = ensure_scratch(ctx, ctx->msm_part[0], ((chunks + ngroups + 1) * W) * Bp * sizeof(XYZZ<F>), &partial);
     if (rc) return rc;
     if (ctx->part_ev_valid[0]) {   // a deferred comb tail may still be reading this buffer
       ZK_HIP(hipStreamWaitEvent(ctx->stream, ctx->part_ev[0], 0));
       ctx->part_ev_valid[0] = false;
     }
-    if ((rc = ensure_scratch(ctx, 12, (size_t)W * n * Bp * sizeof(int16_t), &digits))) return rc;
+    if ((rc = ensure_scratch(ctx, ctx->msm_digits, (size_t)W * n * Bp * sizeof(int16_t), &digits))) return rc;
     XYZZ<F>* mid = (XYZZ<F>*)partial + chunks * W * Bp;
     // window sums: into the caller's buffer when the Horner step is deferred (msm_horner_run)
     XYZZ<F>* wsum = wsum_out ? wsum_out : mid + (size_t)ngroups * W * Bp;
@@ -1186,12 +1186,9 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
   uint32_t per_chunk = (uint32_t)((n + chunks - 1) / chunks);
   chunks = (n + per_chunk - 1) / per_chunk;
   void* partial;
-  // partials + room for the intermediate level of the reduction
-  // side bases own their scratch slot -- 18: commitment MSMs on the second stream, 21: the delta
-  // multiples on the assembly stream --: the main stream may be running an MSM on slot 6 at the
-  // same time
-  int rc = ensure_scratch(ctx, bases->side == 2 ? 21 : bases->side ? 18 : 6,
-                          (chunks + 256) * Bp * sizeof(XYZZ<F>), &partial);
+  // partials + room for the intermediate level of the reduction; side bases have their own
+  DevBuf& part = bases->side == 2 ? ctx->side_part3 : bases->side ? ctx->side_part2 : ctx->msm_part[0];
+  int rc = ensure_scratch(ctx, part, (chunks + 256) * Bp * sizeof(XYZZ<F>), &partial);
   if (rc) return rc;
   if (!bases->side && ctx->part_ev_valid[0]) {   // a deferred tail of an earlier MSM may still be reading this buffer
     ZK_HIP(hipStreamWaitEvent(ctx->stream, ctx->part_ev[0], 0));

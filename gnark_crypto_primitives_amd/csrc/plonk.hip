@@ -524,10 +524,8 @@ struct RoundTmp {
 int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
                       size_t batch, const void* blind, void* commits_out, int32_t* status_out) {
   ZK_HIP(hipSetDevice(ctx->device));
-  if (ctx->sets[0].pending || ctx->sets[1].pending) {
-    ctx->err = "a submitted Groth16 batch is in flight; collect it first";
-    return ZKMI_ERR_ARG;
-  }
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
   if (batch == 0 || batch > pk->max_batch) {
     ctx->err = "plonk: batch must be in [1, max_batch]";
     return ZKMI_ERR_ARG;
@@ -540,7 +538,6 @@ int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const
   pk->batch = batch;
   pk->Bp = Bp;
   pk->round = 0;
-  int rc;
   for (auto& b : pk->cf)
     if ((rc = buf(ctx, b, (n + 8) * Bp * 32))) return rc;
   for (auto& b : pk->big)
@@ -563,7 +560,7 @@ int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const
   Fr* slots = (Fr*)pk->big[0].p;
   Fr *A = (Fr*)pk->big[1].p, *B = (Fr*)pk->big[2].p, *C = (Fr*)pk->big[3].p;
   void* st;
-  if ((rc = ensure_scratch(ctx, 5, Bp * 4, &st))) return rc;
+  if ((rc = ensure_scratch(ctx, ctx->sets[0].misc, Bp * 4, &st))) return rc;
   rc = transpose_in(ctx, in_dev, slots + Bp, n_in, batch, Bp, 32);
   // the inputs in gnark's image, for PI(X) in round 3: big[5] rows 0 .. n_pub - 1 are the public ones
   if (!rc) rc = transpose_in(ctx, in_dev, pk->big[5].p, n_in, batch, Bp, 32);

@@ -399,59 +399,20 @@ int zkmi_prove_witness_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs*
     ctx->err = "prove_witness_submit: n_constraints must be in [1, 2^log_n]";
     return ZKMI_ERR_ARG;
   }
-  const int si = ctx->next_submit;
-  zkmi_ctx::ProveSet& S = ctx->sets[si];
-  if (S.pending) {
-    ctx->err = "prove: two batches already in flight; collect one first";
-    return ZKMI_ERR_ARG;
-  }
-  const size_t Bp = round_up(batch, 64);
-  const size_t nw = pk->n_wires;
-  int rc;
-  const int base = si == 0 ? 0 : 8;
-  void* misc;
-  // the same scratch slots as zkmi_prove_submit (value file = wire matrix here), so the two entry
-  // points share one HBM plan; the idle set is sized too, so steady-state submits never allocate
-  const size_t sums_bytes = Bp * (7 * 128 + 2 * 256 + 256 + 256 * (4 * 128 + 256));
-  if (!ctx->sets[si ^ 1].pending) {
-    void* dummy;
-    const int ob = si == 0 ? 8 : 0;
-    if ((rc = ensure_scratch(ctx, ob + 0, nw * Bp * 32, &dummy)) ||
-        (rc = ensure_scratch(ctx, ob + 1, n * Bp * 32, &dummy)) ||
-        (rc = ensure_scratch(ctx, ob + 2, n * Bp * 32, &dummy)) ||
-        (rc = ensure_scratch(ctx, ob + 3, n * Bp * 32, &dummy)) ||
-        (rc = ensure_scratch(ctx, ob + 5, Bp * (96 + 4) + batch * 64, &dummy)) ||
-        (rc = ensure_scratch(ctx, si == 0 ? 15 : 14, sums_bytes, &dummy)))
-      return rc;
-  }
-  if ((rc = ensure_scratch(ctx, si == 0 ? 14 : 15, sums_bytes, &S.sums)) ||
-      (rc = ensure_scratch(ctx, base + 0, nw * Bp * 32, &S.slots)) ||
-      (rc = ensure_scratch(ctx, base + 1, n * Bp * 32, &S.a)) ||
-      (rc = ensure_scratch(ctx, base + 2, n * Bp * 32, &S.b)) ||
-      (rc = ensure_scratch(ctx, base + 3, n * Bp * 32, &S.c)) ||
-      (rc = ensure_scratch(ctx, base + 5, Bp * (96 + 4) + batch * 64, &misc)))
-    return rc;
-  S.rs = misc;
-  S.st = (char*)misc + Bp * 96;
-  char* stage_rs = (char*)misc + Bp * 100;
-  S.heavy_enqueued = false;
-  hipStream_t saved = ctx->stream;
-  ctx->stream = ctx->stream2;   // the helpers launch on ctx->stream
-  hipEventRecord(S.ev0, ctx->stream);
-  rc = stage_rows(ctx, wires, nw, batch, Bp, S.slots);
+  // the value file is the wire matrix here; no inputs are staged through misc besides r/s
+  hipStream_t main;
+  int rc = prove_set_begin(ctx, pk, pk->n_wires, 0, batch, rs, &main, nullptr);
+  if (rc) return rc;
+  zkmi_ctx::ProveSet& S = ctx->sets[ctx->next_submit];
+  const size_t Bp = S.Bp;
+  S.cs = nullptr;
+  S.n_constraints = n_constraints;
+  S.f_domain = false;
+  rc = stage_rows(ctx, wires, pk->n_wires, batch, Bp, S.slots.p);
   if (!rc && !r1cs) {
-    rc = stage_rows(ctx, a, n_constraints, batch, Bp, S.a);
-    if (!rc) rc = stage_rows(ctx, b, n_constraints, batch, Bp, S.b);
-    if (!rc) rc = stage_rows(ctx, c, n_constraints, batch, Bp, S.c);
-  }
-  if (!rc) {
-    const void* rs_dev = rs;
-    if (pointer_kind(rs) != PTR_DEVICE) {
-      if (hipMemcpyAsync(stage_rs, rs, batch * 64, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        rc = ZKMI_ERR_HIP;
-      rs_dev = stage_rs;
-    }
-    if (!rc) rc = transpose_in(ctx, rs_dev, S.rs, 2, batch, Bp, 32);
+    rc = stage_rows(ctx, a, n_constraints, batch, Bp, S.a.p);
+    if (!rc) rc = stage_rows(ctx, b, n_constraints, batch, Bp, S.b.p);
+    if (!rc) rc = stage_rows(ctx, c, n_constraints, batch, Bp, S.c.p);
   }
   if (!rc && hipMemsetAsync(S.st, 0, Bp * 4, ctx->stream) != hipSuccess) rc = ZKMI_ERR_HIP;
   if (!rc && r1cs) {
@@ -464,30 +425,16 @@ int zkmi_prove_witness_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs*
     m.n_constraints = r1cs->n_constraints;
     hipLaunchKernelGGL(r1cs_eval_kernel,
                        dim3((unsigned)(Bp / 64), (unsigned)std::min<size_t>((n_constraints + 3) / 4, 32768)),
-                       dim3(256), 0, ctx->stream, m, (const Fr*)S.slots, (Fr*)S.a, (Fr*)S.b, (Fr*)S.c,
-                       (int32_t*)S.st, Bp);
+                       dim3(256), 0, ctx->stream, m, (const Fr*)S.slots.p, (Fr*)S.a.p, (Fr*)S.b.p,
+                       (Fr*)S.c.p, (int32_t*)S.st, Bp);
     if (hipGetLastError() != hipSuccess) rc = ZKMI_ERR_HIP;
   }
-  S.batch = batch;
-  S.Bp = Bp;
-  S.pk = pk;
-  S.cs = nullptr;
-  S.n_constraints = n_constraints;
-  S.f_domain = false;
   // commitment extension: the caller's solver has produced the commitment wires; the proof still
   // needs the Pedersen commitments themselves and (several commitments) the folding challenge
   for (size_t i = 0; !rc && i < pk->commits.size(); i++) rc = commit_phase(ctx, S, (uint32_t)i, false);
   if (!rc && !pk->commits.empty()) rc = commit_finish_submit(ctx, S);
-  hipEventRecord(S.ev1, ctx->stream);
-  ctx->stream = saved;
-  if (rc) {
-    if (rc == ZKMI_ERR_HIP && ctx->err.empty()) ctx->err = "prove_witness_submit: HIP error while staging";
-    hipStreamSynchronize(ctx->stream2);   // nothing of a failed submit stays queued on caller memory
-    return rc;
-  }
-  S.pending = true;
-  ctx->next_submit ^= 1;
-  return ZKMI_OK;
+  if (rc == ZKMI_ERR_HIP && ctx->err.empty()) ctx->err = "prove_witness_submit: HIP error while staging";
+  return prove_set_end(ctx, main, rc);
 }
 
 // The blocking form (round 2's entry point): one submit + collect.
@@ -495,21 +442,20 @@ int zkmi_prove_witness_batch(zkmi_ctx* ctx, const zkmi_pk* pk, const void* wires
                              const void* b, const void* c, size_t n_constraints, size_t batch,
                              const void* rs, void* proofs_out) {
   if (batch == 0) return ZKMI_OK;
-  if (ctx->sets[0].pending || ctx->sets[1].pending) {
-    ctx->err = "prove_witness_batch: submitted batches are still in flight";
-    return ZKMI_ERR_ARG;
-  }
-  if (!proofs_out) {
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
+  if (!pk || !proofs_out) {
     ctx->err = "prove_witness_batch: null argument";
     return ZKMI_ERR_ARG;
   }
-  int rc = zkmi_prove_witness_submit(ctx, pk, nullptr, wires, a, b, c, n_constraints, batch, rs);
-  if (rc) return rc;
+  // checked before the submit: a refused call leaves no batch in flight
   if (!pk->commits.empty()) {
     ctx->err = "prove_witness_batch: this key has commitments: use zkmi_prove_witness_submit + "
                "zkmi_prove_collect_ex";
     return ZKMI_ERR_ARG;
   }
+  if ((rc = zkmi_prove_witness_submit(ctx, pk, nullptr, wires, a, b, c, n_constraints, batch, rs)))
+    return rc;
   std::vector<int32_t> status(batch);
   return zkmi_prove_collect(ctx, proofs_out, status.data());
 }

@@ -54,8 +54,17 @@ struct zkmi_ctx {
   std::vector<zk::NttPlan> plans;
   hipEvent_t ev[8] = {};
   double timings[8] = {};
-  // scratch arena for the prove pipeline, grown on demand
-  zk::DevBuf scratch[24];
+  // HBM working set shared by both pipeline sets, grown on demand (ensure_scratch), freed in
+  // zkmi_destroy.  These run on the main stream only, so consecutive batches queue up behind
+  // each other:
+  zk::DevBuf ntt_tmp;                // NTT temporary of the quotient
+  zk::DevBuf build_tmp;              // table-build inversion scratch; proof-of-knowledge temporary
+  zk::DevBuf msm_digits, msm_sint;   // MSM digits, integer scalars
+  zk::DevBuf msm_part[2];            // MSM chunk partials; [1] only for deferred tails (part_ev)
+  // Side bases (zkmi_msm_bases::side) run while the main stream may be running an MSM on
+  // msm_part[0], so each side stream has its own partials:
+  zk::DevBuf side_part2;             // stream2: commitment MSMs of a submit
+  zk::DevBuf side_part3;             // stream3: multiples of delta beside the assembly
   // software pipeline over batches: the latency-bound witness solve of batch k+1 runs on
   // `stream2` (16 wavefronts at batch 1024) underneath the NTT/MSM kernels of batch k.
   // `stream3` runs the 16-wavefront assembly of batch k underneath the quotient kernels of batch k+1.
@@ -63,7 +72,11 @@ struct zkmi_ctx {
   struct ProveSet {
     bool pending = false;
     bool heavy_enqueued = false;   // quotient + MSMs of this batch are already on the main stream
-    void* sums = nullptr;          // MSM results, delta multiples, assembled proofs
+    // Buffers owned by the set, sized by prove_set_begin (set 0's are also borrowed by the
+    // standalone entry points, see require_idle); a pending set's are never regrown.
+    // misc = r/s, status and staged inputs; sums = MSM results, delta multiples, window sums,
+    // assembled proofs (SumsView); commit = commitment buffers (commit.hip)
+    zk::DevBuf slots, a, b, c, misc, sums, commit;
     hipEvent_t evq[5] = {};        // main stream: start, after NTTs, after G1 MSMs, after G2, done
     hipEvent_t eva[2] = {};        // stream3: assembly start / end
     hipEvent_t msm_ev[8][2] = {};  // around every proving-key msm_accumulate launch
@@ -74,11 +87,12 @@ struct zkmi_ctx {
     const zkmi_cs* cs = nullptr;      // null for zkmi_prove_witness_batch (solved by the caller)
     size_t n_constraints = 0;         // rows of a, b, c that hold data (the rest of the domain is 0)
     bool f_domain = true;             // value file and a, b, c in the solver's 2^261 domain
-    void *slots = nullptr, *a = nullptr, *b = nullptr, *c = nullptr, *rs = nullptr, *st = nullptr;
+    void *rs = nullptr, *st = nullptr;        // r/s and status, carved from misc
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // solve start / end on stream2
-    // commitment extension: Pedersen commitments of the batch (n_commitments x Bp G1 affine) and
-    // the per-proof powers of the folding challenge (n_commitments x Bp fr, in the value file's
-    // domain), written by the submit; proof of knowledge (Bp XYZZ -> affine) by the collect
+    // commitment extension, carved from `commit`: Pedersen commitments of the batch
+    // (n_commitments x Bp G1 affine) and the per-proof powers of the folding challenge
+    // (n_commitments x Bp fr, in the value file's domain), written by the submit; proof of
+    // knowledge (Bp XYZZ -> affine) by the collect
     void *commit_pts = nullptr, *commit_ch = nullptr, *commit_pok = nullptr, *commit_acc = nullptr;
     std::vector<zk::Fr> commit_host;   // commitment wire values (plain integers), n x batch
   } sets[2];
@@ -219,11 +233,24 @@ enum { OP_END = 0, OP_ADD, OP_SUB, OP_MUL, OP_MULC, OP_ADDC, OP_NEG, OP_INV, OP_
 
 static inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
-int ensure_scratch(zkmi_ctx* ctx, int slot, size_t bytes, void** out);
+// grows `buf` to at least `bytes` (synchronising the context's streams first if it held memory)
+int ensure_scratch(zkmi_ctx* ctx, DevBuf& buf, size_t bytes, void** out = nullptr);
+// ZKMI_OK when no Groth16 batch is in flight, else ZKMI_ERR_ARG with ctx->err set
+int require_idle(zkmi_ctx* ctx);
 // where a caller's pointer lives (hipPointerGetAttributes)
 enum { PTR_PAGEABLE = 0, PTR_PINNED = 1, PTR_DEVICE = 2 };
 int pointer_kind(const void* p);
 void witness_ring_free(zkmi_ctx* ctx);
+
+// One Groth16 submit (zkmi_prove_submit, zkmi_prove_witness_submit) on set ctx->next_submit.
+// prove_set_begin sizes that set and the idle one (value file of `value_rows`, `n_staged` input
+// rows staged through misc), stages r/s, and switches ctx->stream to stream2 (saved in *main)
+// after recording ev0; *stage = the set's staging area for host inputs.  On failure nothing is
+// left switched.  prove_set_end(rc) records ev1 and restores the stream; the set becomes pending
+// when rc == 0, otherwise stream2 is drained so that nothing queued still reads caller memory.
+int prove_set_begin(zkmi_ctx* ctx, const zkmi_pk* pk, size_t value_rows, size_t n_staged,
+                    size_t batch, const void* rs, hipStream_t* main, char** stage);
+int prove_set_end(zkmi_ctx* ctx, hipStream_t main, int rc);
 
 // layout conversion (proof-major <-> batch-inner), rows x batch elements of `elem_bytes`
 int transpose_in(zkmi_ctx* ctx, const void* src_pm, void* dst_bi, size_t rows, size_t batch,
@@ -288,6 +315,8 @@ int solve_rows(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr* b, Fr* c,
                size_t Bp, uint32_t row_begin, uint32_t row_end);
 
 // commit.hip: commitment extension of the prover
+// bytes of a set's commitment buffers for a key with n_commitments (0 for a plain key)
+size_t commit_buffer_bytes(size_t n_commitments, size_t Bp);
 // the commitments of set S at a COMMIT row of the solver path (or all of them, witness path):
 // MSM over the key's basis from the value file, hash_to_field on the host, challenge into the wire
 int commit_phase(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S, uint32_t index, bool write_wire);

@@ -51,6 +51,15 @@ def _check(zk_ctx, cc, asg, bad, seed, wbits=(7, 5), publics=None, **plan):
         p2, s2, c2 = prover.collect()
         assert not s2.any() and np.array_equal(p2, want[good])
         assert np.array_equal(c2[:, :-1], wcoms[good]) and np.array_equal(c2[:, -1], wpoks[good])
+        # the blocking witness entry refuses a key with commitments before it submits anything
+        # (other r, s here): the context stays idle and the next submit + collect is its own batch
+        zero = np.zeros((len(good), cc.n_constraints, 4), np.uint64)
+        with pytest.raises(lib.ZkmiError):
+            prover.prove_witness(W, zero, zero, zero, np.ascontiguousarray(rs[good][::-1]))
+        prover.submit_witness(W, np.ascontiguousarray(rs[good]))
+        p3, s3, c3 = prover.collect()
+        assert not s3.any() and np.array_equal(p3, want[good])
+        assert np.array_equal(c3[:, :-1], wcoms[good]) and np.array_equal(c3[:, -1], wpoks[good])
         with pytest.raises(lib.ZkmiError):      # the plain collect refuses a key with commitments
             prover.ctx.prove_submit(prover.pk_h, prover.cs_h, inp, len(asg), rs)
             try:

@@ -66,6 +66,14 @@ def test_witness_submit_small_all_memory_kinds(zk_ctx, wbits):
             p4, _ = prover.collect()
             p5, s5 = prover.collect()
             assert np.array_equal(p4, want) and np.array_equal(p5, want) and not s5.any()
+            # the solver entry and the witness entry in flight together on one context: both
+            # submit into the same two pipeline sets under one HBM plan
+            prover.submit(inp, rs)
+            prover.submit_witness(W, rs)
+            p7, s7 = prover.collect()
+            p8, s8 = prover.collect()
+            assert not s7.any() and not s8.any()
+            assert np.array_equal(p7, want) and np.array_equal(p8, want), (wbits, batch)
             # the blocking round-2 entry is the same path
             assert np.array_equal(prover.prove_witness(W, A, B, Cc, rs), want)
             # a wire vector that does not satisfy the system: flagged per proof by the device's
