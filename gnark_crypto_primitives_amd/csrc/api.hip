@@ -655,7 +655,7 @@ int zkmi_msm_batch(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const void* scala
       (rc = ensure_scratch(ctx, ctx->sets[0].c, Bp * pt, &aff)))
     return rc;
   if ((rc = transpose_in(ctx, ss.dev, sbi, n, batch, Bp, 32))) return rc;
-  if ((rc = msm_run(ctx, bases, (const Fr*)sbi, nullptr, Bp, acc))) return rc;
+  if ((rc = msm_run(ctx, bases, (const Fr*)sbi, nullptr, Bp, batch, acc))) return rc;
   if ((rc = xyzz_to_affine(ctx, bases->group, acc, aff, Bp))) return rc;
   ZK_HIP(hipMemcpyAsync(so.dev, aff, batch * pt, hipMemcpyDeviceToDevice, ctx->stream));
   if ((rc = so.finish())) return rc;
@@ -684,7 +684,7 @@ int zkmi_fixed_base_mul(zkmi_ctx* ctx, int group, const void* base, const void* 
     return rc;
   }
   rc = transpose_in(ctx, ss.dev, sbi, 1, n, Bp, 32);   // one row of n scalars, batch-inner
-  if (!rc) rc = msm_run(ctx, b, (const Fr*)sbi, nullptr, Bp, acc);
+  if (!rc) rc = msm_run(ctx, b, (const Fr*)sbi, nullptr, Bp, n, acc);
   if (!rc) rc = xyzz_to_affine(ctx, group, acc, aff, Bp);
   if (!rc) {
     hipMemcpyAsync(so.dev, aff, n * pt, hipMemcpyDeviceToDevice, ctx->stream);
@@ -1305,7 +1305,7 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
   zkmi_ctx::ProveSet& S = ctx->sets[si];
   const zkmi_pk* pk = S.pk;
   const bool fd = S.f_domain;
-  const size_t Bp = S.Bp, n = (size_t)1 << pk->log_n;
+  const size_t Bp = S.Bp, batch = S.batch, n = (size_t)1 << pk->log_n;
   NttPlan* plan;
   int rc = get_plan(ctx, (int)pk->log_n, &plan);
   if (rc) return rc;
@@ -1327,15 +1327,15 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
   const bool d1 = pk->Z->plan.shared || pk->Z->plan.comb;
   const bool d2 = pk->B2->plan.shared || pk->B2->plan.comb;
   hipStream_t q3 = ctx->stream3;
-  if ((rc = msm_run(ctx, pk->A, slots, pk->a_wire, Bp, v.sA, fd, d1 ? v.w1[0] : nullptr, q3)) ||
-      (rc = msm_run(ctx, pk->B1, slots, pk->b_wire, Bp, v.sB1, fd, d1 ? v.w1[1] : nullptr, q3)) ||
-      (rc = msm_run(ctx, pk->K, slots, pk->k_wire, Bp, v.sK, fd, d1 ? v.w1[2] : nullptr, q3)) ||
-      (rc = msm_run(ctx, pk->Z, h, nullptr, Bp, v.sZ, false, d1 ? v.w1[3] : nullptr, q3))) {
+  if ((rc = msm_run(ctx, pk->A, slots, pk->a_wire, Bp, batch, v.sA, fd, d1 ? v.w1[0] : nullptr, q3)) ||
+      (rc = msm_run(ctx, pk->B1, slots, pk->b_wire, Bp, batch, v.sB1, fd, d1 ? v.w1[1] : nullptr, q3)) ||
+      (rc = msm_run(ctx, pk->K, slots, pk->k_wire, Bp, batch, v.sK, fd, d1 ? v.w1[2] : nullptr, q3)) ||
+      (rc = msm_run(ctx, pk->Z, h, nullptr, Bp, batch, v.sZ, false, d1 ? v.w1[3] : nullptr, q3))) {
     ctx->msm_ev_set = -1;
     return rc;
   }
   hipEventRecord(S.evq[2], ctx->stream);
-  rc = msm_run(ctx, pk->B2, slots, pk->b_wire, Bp, v.sB2, fd, d2 ? v.w2 : nullptr, q3);
+  rc = msm_run(ctx, pk->B2, slots, pk->b_wire, Bp, batch, v.sB2, fd, d2 ? v.w2 : nullptr, q3);
   ctx->msm_ev_set = -1;
   if (rc) return rc;
   hipEventRecord(S.evq[3], ctx->stream);
@@ -1348,10 +1348,10 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
     ZK_HIP(hipStreamWaitEvent(q3, S.ev1, 0));   // r, s staged by the submit
     ctx->stream = q3;
     hipLaunchKernelGGL(rs_prep_kernel, dim3((unsigned)(Bp / 64)), dim3(64), 0, q3, rs_bi, Bp);
-    (void)((rc = msm_run(ctx, pk->D1, rs_bi, pk->idx3 + 0, Bp, v.tR)) ||
-           (rc = msm_run(ctx, pk->D1, rs_bi, pk->idx3 + 1, Bp, v.tS)) ||
-           (rc = msm_run(ctx, pk->D1, rs_bi, pk->idx3 + 2, Bp, v.tNRS)) ||
-           (rc = msm_run(ctx, pk->D2, rs_bi, pk->idx3 + 1, Bp, v.tS2)));
+    (void)((rc = msm_run(ctx, pk->D1, rs_bi, pk->idx3 + 0, Bp, batch, v.tR)) ||
+           (rc = msm_run(ctx, pk->D1, rs_bi, pk->idx3 + 1, Bp, batch, v.tS)) ||
+           (rc = msm_run(ctx, pk->D1, rs_bi, pk->idx3 + 2, Bp, batch, v.tNRS)) ||
+           (rc = msm_run(ctx, pk->D2, rs_bi, pk->idx3 + 1, Bp, batch, v.tS2)));
     ctx->stream = main_stream;
     if (rc) return rc;
   }

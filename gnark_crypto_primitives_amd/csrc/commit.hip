@@ -242,7 +242,8 @@ int commit_phase(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S, uint32_t index, bool writ
   G1Affine* pts = (G1Affine*)S.commit_pts + index * Bp;
   if (ck.n_private == 0) {   // nothing private committed: the commitment is the point at infinity
     ZK_HIP(hipMemsetAsync(pts, 0, Bp * 64, ctx->stream));
-  } else if ((rc = msm_run(ctx, ck.basis, (const Fr*)S.slots.p, ck.private_dev, Bp, acc, S.f_domain)) ||
+  } else if ((rc = msm_run(ctx, ck.basis, (const Fr*)S.slots.p, ck.private_dev, Bp, batch, acc,
+                           S.f_domain)) ||
              (rc = xyzz_to_affine(ctx, 1, acc, pts, Bp))) {
     return rc;
   }
@@ -316,14 +317,16 @@ int commit_finish_submit(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S) {
 
 int commit_pok(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S) {
   const zkmi_pk* pk = S.pk;
-  const size_t n = pk->commits.size(), Bp = S.Bp;
+  const size_t n = pk->commits.size(), Bp = S.Bp, batch = S.batch;
   if (n == 0) return ZKMI_OK;
   int rc;
   G1XYZZ* pok = (G1XYZZ*)S.commit_pok;
   G1Affine* pok_aff = (G1Affine*)((char*)S.commit_pok + Bp * 128);
   if (n == 1 && pk->commits[0].n_private) {
     const zkmi_commit_key& ck = pk->commits[0];
-    if ((rc = msm_run(ctx, ck.sigma, (const Fr*)S.slots.p, ck.private_dev, Bp, pok, S.f_domain))) return rc;
+    if ((rc = msm_run(ctx, ck.sigma, (const Fr*)S.slots.p, ck.private_dev, Bp, batch, pok,
+                      S.f_domain)))
+      return rc;
   } else {
     size_t mx = 1;
     for (auto& ck : pk->commits) mx = std::max<size_t>(mx, ck.n_private);
@@ -344,7 +347,7 @@ int commit_pok(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S) {
                            dim3(256), 0, ctx->stream, (const Fr*)S.slots.p, ck.private_dev,
                            (const Fr*)((char*)S.commit_ch + i * Bp * 32), (Fr*)tmp, ck.n_private, Bp,
                            S.f_domain ? 1 : 0);
-      if ((rc = msm_run(ctx, ck.sigma, (const Fr*)tmp, nullptr, Bp, part, S.f_domain))) return rc;
+      if ((rc = msm_run(ctx, ck.sigma, (const Fr*)tmp, nullptr, Bp, batch, part, S.f_domain))) return rc;
       hipLaunchKernelGGL(xyzz_add_kernel, dim3((unsigned)(Bp / 64)), dim3(64), 0, ctx->stream, pok,
                          (const G1XYZZ*)part, Bp, i == 0 ? 1 : 0);
     }

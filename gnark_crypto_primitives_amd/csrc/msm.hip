@@ -15,7 +15,8 @@
 //   * comb tables (default for keys of >= 4096 bases): a joint table of all subset sums of every
 //     group of k consecutive bases, 254 one-bit windows: 254 / k additions per (base, proof)
 //     (k = 18 / 19 for the Arbo-160 key).  Window index = a grid dimension; the 254 window sums of
-//     a proof are combined by Horner's rule.
+//     a proof are combined by Horner's rule.  Groups whose scalars are the same in every proof of
+//     the batch are summed once per batch (comb_common_sums), the others per lane.
 //   * one shared table per base (d * P, d = 1..2^(c-1)), ceil(255 / c) signed-digit windows with
 //     their own accumulators, Horner combine (explicit window_bits 100 + c).
 //   * per-window tables (d * 2^(shift_j) * P for every window j), all windows into one
@@ -497,19 +498,32 @@ __global__ __launch_bounds__(64) void comb_build(const Affine<F>* __restrict__ b
 // Bit j of C is base i's sign in window j; the parity e rides in bit 255 and becomes the sign
 // pattern of one extra window (index 254) whose sum is subtracted once at the end together with
 // the sum of all bases:  sum_i s_i P_i = 2 H - W_254 - S,  H = sum_j 2^j W_j  (msm_horner_comb).
+//
+// gvar[g] (zeroed before the launch) is set to 1 when a scalar of group g = i / k differs from
+// lane 0's within the first `batch` lanes; padding lanes do not take part.  The raw Montgomery
+// words are compared: equal words convert to equal integers, so a group left at 0 has the same
+// digits in every proof of the batch (comb_split_kernel).
 template <bool SIGNED>
 __global__ __launch_bounds__(256) void comb_scalars_kernel(const Fr* __restrict__ scalars,
                                                            const uint32_t* __restrict__ row_idx,
                                                            size_t Bp, uint32_t n, int32_t kmul32,
                                                            const uint8_t* __restrict__ inf,
-                                                           Fr* __restrict__ out) {
+                                                           Fr* __restrict__ out, size_t batch,
+                                                           uint32_t k, uint32_t* __restrict__ gvar) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (uint32_t i = blockIdx.y; i < n; i += gridDim.y) {
     Fr s = Fr::zero();
     if (!inf[i]) {   // the point at infinity contributes nothing: its bits never matter
       Fr29 kk = Fr29::zero();
       kk.v[0] = kmul32;
-      const Fr raw = bi_ld(scalars, row_idx ? row_idx[i] : i, b, Bp);
+      const uint32_t row = row_idx ? row_idx[i] : i;
+      const Fr raw = bi_ld(scalars, row, b, Bp);
+      const Fr raw0 = bi_ld(scalars, row, 0, Bp);   // wave-uniform
+      uint32_t diff = 0;
+#pragma unroll
+      for (int l = 0; l < 8; l++) diff |= raw.v[l] ^ raw0.v[l];
+      // one plain store per wave; waves that race write the same value
+      if (__ballot(b < batch && diff != 0) != 0 && (threadIdx.x & 63u) == 0) gvar[i / k] = 1u;
       pack_canonical<Fr29Params>(s.v, mul(unpack29<Fr29Params>(raw.v), kk));
       if (SIGNED) {
         // t = (s + (s odd ? r : 0)) >> 1      (s + r < 2^255)
@@ -544,17 +558,69 @@ __global__ __launch_bounds__(256) void comb_scalars_kernel(const Fr* __restrict_
   }
 }
 
-// digits[j][g][b] = sum_i bit_j(s[gk+i][b]) << i.  SIGNED: k-bit sign pattern M -> (index, negate):
-// top bit set: entry M & (2^(k-1) - 1); clear: entry ~M & (2^(k-1) - 1), negated (bit 31 of the
-// digit).  Window 254 takes bit 255 of the rewritten scalars (the parity pattern).
+// Splits the groups by gvar: vlist / ulist = the varying / uniform groups in increasing order,
+// vpos[g] = position of g in vlist (~0u: uniform), counts = {|vlist|, |ulist|}.  One workgroup of
+// 1024 threads walks the groups in tiles; the counts stay on the device (the accumulate and
+// common-sum grids are sized from n_groups and read them there).
+static __global__ __launch_bounds__(1024) void comb_split_kernel(const uint32_t* __restrict__ gvar,
+                                                                 uint32_t n_groups,
+                                                                 uint32_t* __restrict__ vlist,
+                                                                 uint32_t* __restrict__ ulist,
+                                                                 uint32_t* __restrict__ vpos,
+                                                                 uint32_t* __restrict__ counts) {
+  __shared__ uint32_t wave_nv[16];
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  uint32_t nv = 0, nu = 0;
+  for (uint32_t g0 = 0; g0 < n_groups; g0 += 1024) {
+    const uint32_t g = g0 + t;
+    const bool live = g < n_groups;
+    const bool var = live && gvar[g] != 0;
+    const unsigned long long vm = __ballot(var);
+    if (lane == 0) wave_nv[w] = (uint32_t)__popcll(vm);
+    __syncthreads();
+    uint32_t before = 0, tile_nv = 0;
+    for (uint32_t q = 0; q < 16; q++) {
+      before += q < w ? wave_nv[q] : 0u;
+      tile_nv += wave_nv[q];
+    }
+    // varying groups of this tile below g; every group of the tile below g exists
+    const uint32_t vb = before + (uint32_t)__popcll(vm & ((1ull << lane) - 1ull));
+    if (var) {
+      vlist[nv + vb] = g;
+      vpos[g] = nv + vb;
+    } else if (live) {
+      ulist[nu + t - vb] = g;
+      vpos[g] = ~0u;
+    }
+    const uint32_t tile = n_groups - g0 < 1024u ? n_groups - g0 : 1024u;
+    nv += tile_nv;
+    nu += tile - tile_nv;
+    __syncthreads();   // wave_nv is rewritten by the next tile
+  }
+  if (t == 0) {
+    counts[0] = nv;
+    counts[1] = nu;
+  }
+}
+
+// digits[j][p][b] = sum_i bit_j(s[gk+i][b]) << i for the varying group g = vlist[p].  SIGNED: k-bit
+// sign pattern M -> (index, negate): top bit set: entry M & (2^(k-1) - 1); clear: entry
+// ~M & (2^(k-1) - 1), negated (bit 31 of the digit).  Window 254 takes bit 255 of the rewritten
+// scalars (the parity pattern).  A uniform group has lane 0's digits in every proof: only the
+// first wave of the blocks at x = 0 transposes it, and lane 0 writes d0[j][g] (comb_common_sums).
 template <int KMAX, bool SIGNED>
 __global__ __launch_bounds__(256) void comb_digits_kernel(const Fr* __restrict__ sint, size_t Bp,
                                                           uint32_t n, uint32_t k, uint32_t n_groups,
-                                                          uint32_t* __restrict__ digits) {
+                                                          const uint32_t* __restrict__ vpos,
+                                                          uint32_t* __restrict__ digits,
+                                                          uint32_t* __restrict__ d0) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint4* base = reinterpret_cast<const uint4*>(sint);
   const uint32_t low = (1u << (k - 1)) - 1u;
   for (uint32_t g = blockIdx.y; g < n_groups; g += gridDim.y) {
+    const uint32_t p = vpos[g];
+    const bool uni = p == ~0u;
+    if (uni && (blockIdx.x != 0 || threadIdx.x >= 64)) continue;   // wave-uniform
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       uint4 wv[KMAX];
@@ -594,41 +660,111 @@ __global__ __launch_bounds__(256) void comb_digits_kernel(const Fr* __restrict__
           }
           uint32_t idx = m[bit];
           if (SIGNED) idx = ((idx >> (k - 1)) & 1u) ? (idx & low) : ((~idx & low) | 0x80000000u);
-          digits[((size_t)j * n_groups + g) * Bp + b] = idx;
+          if (!uni)
+            digits[((size_t)j * n_groups + p) * Bp + b] = idx;
+          else if (b == 0)
+            d0[(size_t)j * n_groups + g] = idx;
         }
       }
     }
   }
 }
 
-// grid: x over proofs, y over the windows (254, or 255 for signed tables), z over chunks of groups
+// grid: x over proofs, y over the windows (254, or 255 for signed tables), z over chunks of the
+// varying groups: the grid is sized from n_groups, each block takes its share of counts[0]
+// (an empty chunk leaves the identity)
 template <class F, bool CHECK_INF, bool SIGNED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void
 msm_accumulate_comb(const Affine<F>* __restrict__ table, const uint32_t* __restrict__ digits,
-                    size_t Bp, uint32_t n_groups, uint32_t per_chunk, uint32_t per_group,
+                    size_t Bp, uint32_t n_groups, const uint32_t* __restrict__ vlist,
+                    const uint32_t* __restrict__ counts, uint32_t per_group,
                     XYZZ<F>* __restrict__ partial) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t chunk = blockIdx.z, j = blockIdx.y;
-  const uint32_t g0 = chunk * per_chunk;
-  uint32_t g1 = g0 + per_chunk;
-  if (g1 > n_groups) g1 = n_groups;
+  const uint32_t nv = counts[0];
+  const uint32_t per_chunk = (nv + gridDim.z - 1) / gridDim.z;
+  const uint32_t p0 = chunk * per_chunk;
+  uint32_t p1 = p0 + per_chunk;
+  if (p1 > nv) p1 = nv;
   const uint32_t* dj = digits + (size_t)j * n_groups * Bp + b;
   __shared__ int32_t zl[CombAcc<F>::LDS_ROWS][256];
   const uint32_t t = threadIdx.x;
   typename CombAcc<F>::type acc = CombAcc<F>::init(zl, t);
-  for (uint32_t g = g0; g < g1; g++) {
-    const uint32_t m = dj[(size_t)g * Bp];
+  for (uint32_t p = p0; p < p1; p++) {
+    const uint32_t m = dj[(size_t)p * Bp];
+    const Affine<F>* tg = table + (size_t)vlist[p] * per_group;
     if (SIGNED) {   // a sign pattern is never "nothing to add"
-      const Affine<F> e = table[(size_t)g * per_group + (m & 0x7fffffffu)];
+      const Affine<F> e = tg[m & 0x7fffffffu];
       if (CHECK_INF && e.is_inf()) continue;
       CombAcc<F>::add(acc, e, (m >> 31) != 0, zl, t);
     } else if (m) {
-      const Affine<F> e = table[(size_t)g * per_group + m];
+      const Affine<F> e = tg[m];
       if (CHECK_INF && e.is_inf()) continue;
       CombAcc<F>::add(acc, e, false, zl, t);
     }
   }
   partial[((size_t)j * gridDim.z + chunk) * Bp + b] = CombAcc<F>::result(acc, zl, t);
+}
+
+// all 32-bit words of a lane's value from lane (lane ^ mask)
+template <class T>
+static __device__ __forceinline__ T shfl_xor_words(const T& x, int mask) {
+  static_assert(sizeof(T) % 4 == 0, "word-sized value");
+  T r;
+  const uint32_t* s = reinterpret_cast<const uint32_t*>(&x);
+  uint32_t* d = reinterpret_cast<uint32_t*>(&r);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / 4); i++) d[i] = (uint32_t)__shfl_xor((int)s[i], mask);
+  return r;
+}
+
+// usum[j] = sum over the uniform groups g = ulist[c] of T[g][d0[j][g]]: the part of window sum j
+// that every proof of the batch shares, added once per lane by the last msm_reduce pass.  One
+// block of 256 lanes per window; each lane sums a strided share of the groups, then a butterfly
+// over the wave and the four wave sums through LDS.  Same entries as msm_accumulate_comb would
+// gather, so the window sums are unchanged (a group sum does not depend on the order).
+template <class F, bool CHECK_INF, bool SIGNED>
+__global__ __launch_bounds__(256) void comb_common_sums(const Affine<F>* __restrict__ table,
+                                                        const uint32_t* __restrict__ d0,
+                                                        uint32_t n_groups,
+                                                        const uint32_t* __restrict__ ulist,
+                                                        const uint32_t* __restrict__ counts,
+                                                        uint32_t per_group,
+                                                        XYZZ<F>* __restrict__ usum) {
+  const uint32_t j = blockIdx.x, t = threadIdx.x;
+  const uint32_t nu = counts[1];
+  const uint32_t* dj = d0 + (size_t)j * n_groups;
+  typename Acc29<F>::type acc = Acc29<F>::type::infinity();
+  for (uint32_t c = t; c < nu; c += blockDim.x) {
+    const uint32_t g = ulist[c];
+    const uint32_t m = dj[g];
+    if (!SIGNED && !m) continue;
+    const Affine<F> e = table[(size_t)g * per_group + (SIGNED ? (m & 0x7fffffffu) : m)];
+    if (CHECK_INF && e.is_inf()) continue;
+    Acc29<F>::add(acc, e, SIGNED && (m >> 31) != 0);
+  }
+  XYZZ<F> s = to_std(acc);
+#pragma unroll 1
+  for (int off = 32; off > 0; off >>= 1) {
+    const XYZZ<F> o = shfl_xor_words(s, off);
+    padd(s, o);
+  }
+  constexpr int NW = (int)(sizeof(XYZZ<F>) / 4);
+  __shared__ uint32_t wave_sum[4][NW];
+  if ((t & 63u) == 0) {
+    const uint32_t* sw = reinterpret_cast<const uint32_t*>(&s);
+    for (int i = 0; i < NW; i++) wave_sum[t >> 6][i] = sw[i];
+  }
+  __syncthreads();
+  if (t == 0) {
+    for (uint32_t q = 1; q < blockDim.x / 64; q++) {
+      XYZZ<F> o;
+      uint32_t* ow = reinterpret_cast<uint32_t*>(&o);
+      for (int i = 0; i < NW; i++) ow[i] = wave_sum[q][i];
+      padd(s, o);
+    }
+    usum[j] = s;
+  }
 }
 
 // out[b] = sum_j 2^j * wsum[j][b], j < W, in two levels so that the dependent chain is short:
@@ -693,12 +829,14 @@ static void launch_comb_horner(hipStream_t stream, const HornerArgsRW<F>& ha, in
 }
 
 // sums groups of `group` consecutive chunk partials: out[g][b] = sum_{k < group} in[g*group + k][b]
-// (blockIdx.z selects an independent set: partial += z * in_zstride, out += z * out_zstride)
+// (blockIdx.z selects an independent set: partial += z * in_zstride, out += z * out_zstride);
+// addend (may be null): addend[z] is added to every sum of set z (comb_common_sums)
 template <class F>
 __global__ __launch_bounds__(64) void msm_reduce(const XYZZ<F>* __restrict__ partial, size_t Bp,
                                                  uint32_t chunks, uint32_t group,
                                                  XYZZ<F>* __restrict__ out, size_t in_zstride,
-                                                 size_t out_zstride) {
+                                                 size_t out_zstride,
+                                                 const XYZZ<F>* __restrict__ addend) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= Bp) return;
   partial += (size_t)blockIdx.z * in_zstride;
@@ -711,6 +849,7 @@ __global__ __launch_bounds__(64) void msm_reduce(const XYZZ<F>* __restrict__ par
     XYZZ<F> p = partial[(size_t)k * Bp + b];
     padd(acc, p);
   }
+  if (addend) padd(acc, addend[blockIdx.z]);
   out[(size_t)blockIdx.y * Bp + b] = acc;
 }
 
@@ -988,7 +1127,7 @@ template <> Affine<Fq2> stotal_of<Fq2>(const zkmi_msm_bases* b) { return b->stot
 
 template <class F>
 int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
-                    const uint32_t* row_idx, size_t Bp, XYZZ<F>* out, bool scalars_f,
+                    const uint32_t* row_idx, size_t Bp, size_t batch, XYZZ<F>* out, bool scalars_f,
                     XYZZ<F>* wsum_out, hipStream_t finish_stream) {
   Fr kmul = Fr::zero();
   kmul.v[0] = 1;  // plain 1: from_mont
@@ -1018,8 +1157,10 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
     // writes the other partial buffer
     const bool defer = wsum_out && finish_stream && finish_stream != ctx->stream;
     const int pb = defer ? (int)(ctx->part_next++ & 1u) : 0;
+    // chunk partials, the intermediate level, the window sums, then the common sums of the uniform
+    // groups (read by the last reduction, which may run on finish_stream: under part_ev as well)
     int rc = ensure_scratch(ctx, ctx->msm_part[pb],
-                            ((chunks + ngroups + 1) * W) * Bp * sizeof(XYZZ<F>), &partial);
+                            ((chunks + ngroups + 1) * W * Bp + W) * sizeof(XYZZ<F>), &partial);
     if (rc) return rc;
     if (ctx->part_ev_valid[pb]) {   // the last reduction that read this buffer must be done
       ZK_HIP(hipStreamWaitEvent(ctx->stream, ctx->part_ev[pb], 0));
@@ -1028,42 +1169,64 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
     // (Measured and dropped: the digit pass one MSM ahead on a fourth stream through two digit
     // buffers -- correct, no gain: the pass is ALU work like the accumulate kernel it would hide
     // under, which slowed down by exactly the pass's 7 ms.)
-    if ((rc = ensure_scratch(ctx, ctx->msm_digits, (size_t)W * G * Bp * sizeof(uint32_t), &digits))) return rc;
+    // digits [W][G][Bp] (the first |vlist| rows of every window are used), then lane 0's digits of
+    // the uniform groups [W][G] and the split of the groups: gvar, vlist, ulist, vpos [G], counts
+    if ((rc = ensure_scratch(ctx, ctx->msm_digits,
+                             ((size_t)W * G * Bp + (size_t)(W + 4) * G + 2) * sizeof(uint32_t),
+                             &digits)))
+      return rc;
     if ((rc = ensure_scratch(ctx, ctx->msm_sint, n * Bp * sizeof(Fr), &sint))) return rc;
+    uint32_t* d0 = (uint32_t*)digits + (size_t)W * G * Bp;
+    uint32_t* gvar = d0 + (size_t)W * G;
+    uint32_t* vlist = gvar + G;
+    uint32_t* ulist = vlist + G;
+    uint32_t* vpos = ulist + G;
+    uint32_t* counts = vpos + G;
     hipStream_t dq = ctx->stream;
     XYZZ<F>* mid = (XYZZ<F>*)partial + chunks * W * Bp;
     XYZZ<F>* wsum = wsum_out ? wsum_out : mid + (size_t)ngroups * W * Bp;
+    XYZZ<F>* usum = (XYZZ<F>*)partial + (chunks + ngroups + 1) * W * Bp;
     const unsigned bx = (Bp % 256 == 0) ? 256 : 64;
     const dim3 sgrid((unsigned)(Bp / bx), (unsigned)(n < 16384 ? n : 16384));
     const dim3 dgrid((unsigned)(Bp / bx), (unsigned)(G < 8192 ? G : 8192));
     const int32_t km = (int32_t)(scalars_f ? 1 : 32);
-    if (sg) {
+    ZK_HIP(hipMemsetAsync(gvar, 0, G * sizeof(uint32_t), dq));
+    if (sg)
       hipLaunchKernelGGL((comb_scalars_kernel<true>), sgrid, dim3(bx), 0, dq, scalars, row_idx, Bp,
-                         (uint32_t)n, km, (const uint8_t*)bases->inf, (Fr*)sint);
-      hipLaunchKernelGGL((comb_digits_kernel<21, true>), dgrid, dim3(bx), 0, dq, (const Fr*)sint, Bp,
-                         (uint32_t)n, k, (uint32_t)G, (uint32_t*)digits);
-    } else {
+                         (uint32_t)n, km, (const uint8_t*)bases->inf, (Fr*)sint, batch, k, gvar);
+    else
       hipLaunchKernelGGL((comb_scalars_kernel<false>), sgrid, dim3(bx), 0, dq, scalars, row_idx, Bp,
-                         (uint32_t)n, km, (const uint8_t*)bases->inf, (Fr*)sint);
+                         (uint32_t)n, km, (const uint8_t*)bases->inf, (Fr*)sint, batch, k, gvar);
+    hipLaunchKernelGGL(comb_split_kernel, dim3(1), dim3(1024), 0, dq, (const uint32_t*)gvar,
+                       (uint32_t)G, vlist, ulist, vpos, counts);
+    if (sg)
+      hipLaunchKernelGGL((comb_digits_kernel<21, true>), dgrid, dim3(bx), 0, dq, (const Fr*)sint, Bp,
+                         (uint32_t)n, k, (uint32_t)G, (const uint32_t*)vpos, (uint32_t*)digits, d0);
+    else
       hipLaunchKernelGGL((comb_digits_kernel<20, false>), dgrid, dim3(bx), 0, dq, (const Fr*)sint,
-                         Bp, (uint32_t)n, k, (uint32_t)G, (uint32_t*)digits);
-    }
+                         Bp, (uint32_t)n, k, (uint32_t)G, (const uint32_t*)vpos, (uint32_t*)digits,
+                         d0);
     zkmi_ctx::ProveSet* es = ctx->msm_ev_set >= 0 ? &ctx->sets[ctx->msm_ev_set] : nullptr;
     const int ev = (es && es->msm_ev_used < 8) ? es->msm_ev_used++ : -1;
-    if (ev >= 0) {
+    if (ev >= 0) {   // brackets the common sums and the accumulate launch: every mixed addition
       es->msm_ev_group[ev] = bases->group;
       hipEventRecord(es->msm_ev[ev][0], ctx->stream);
     }
     const dim3 grid((unsigned)(Bp / bx), (unsigned)W, (unsigned)chunks);
     const uint32_t per_group = 1u << (sg ? k - 1 : k);
 #define ZK_LAUNCH_COMB(CI, SG)                                                                   \
+    hipLaunchKernelGGL((comb_common_sums<F, CI, SG>), dim3((unsigned)W), dim3(256), 0,          \
+                       ctx->stream, (const Affine<F>*)bases->table, (const uint32_t*)d0,        \
+                       (uint32_t)G, (const uint32_t*)ulist, (const uint32_t*)counts, per_group,  \
+                       usum);                                                                    \
     hipLaunchKernelGGL((msm_accumulate_comb<F, CI, SG>), grid, dim3(bx), 0, ctx->stream,        \
                        (const Affine<F>*)bases->table, (const uint32_t*)digits, Bp, (uint32_t)G, \
-                       per_chunk, per_group, (XYZZ<F>*)partial)
+                       (const uint32_t*)vlist, (const uint32_t*)counts, per_group,              \
+                       (XYZZ<F>*)partial)
     if (bases->entries_may_be_inf) {
-      if (sg) ZK_LAUNCH_COMB(true, true); else ZK_LAUNCH_COMB(true, false);
+      if (sg) { ZK_LAUNCH_COMB(true, true); } else { ZK_LAUNCH_COMB(true, false); }
     } else {
-      if (sg) ZK_LAUNCH_COMB(false, true); else ZK_LAUNCH_COMB(false, false);
+      if (sg) { ZK_LAUNCH_COMB(false, true); } else { ZK_LAUNCH_COMB(false, false); }
     }
 #undef ZK_LAUNCH_COMB
     if (ev >= 0) hipEventRecord(es->msm_ev[ev][1], ctx->stream);
@@ -1076,14 +1239,14 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
     if (ngroups > 1) {
       hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), ngroups, (unsigned)W), dim3(64),
                          0, rq, (const XYZZ<F>*)partial, Bp, (uint32_t)chunks, group, mid,
-                         chunks * Bp, (size_t)ngroups * Bp);
+                         chunks * Bp, (size_t)ngroups * Bp, (const XYZZ<F>*)nullptr);
       hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), 1, (unsigned)W), dim3(64), 0,
                          rq, (const XYZZ<F>*)mid, Bp, ngroups, ngroups, wsum,
-                         (size_t)ngroups * Bp, Bp);
+                         (size_t)ngroups * Bp, Bp, (const XYZZ<F>*)usum);
     } else {
       hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), 1, (unsigned)W), dim3(64), 0,
                          rq, (const XYZZ<F>*)partial, Bp, (uint32_t)chunks, (uint32_t)chunks, wsum,
-                         chunks * Bp, Bp);
+                         chunks * Bp, Bp, (const XYZZ<F>*)usum);
     }
     if (defer) {
       ZK_HIP(hipEventRecord(ctx->part_ev[pb], finish_stream));
@@ -1152,14 +1315,14 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
     if (ngroups > 1) {
       hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), ngroups, (unsigned)W), dim3(64),
                          0, ctx->stream, (const XYZZ<F>*)partial, Bp, (uint32_t)chunks, group, mid,
-                         chunks * Bp, (size_t)ngroups * Bp);
+                         chunks * Bp, (size_t)ngroups * Bp, (const XYZZ<F>*)nullptr);
       hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), 1, (unsigned)W), dim3(64), 0,
                          ctx->stream, (const XYZZ<F>*)mid, Bp, ngroups, ngroups, wsum,
-                         (size_t)ngroups * Bp, Bp);
+                         (size_t)ngroups * Bp, Bp, (const XYZZ<F>*)nullptr);
     } else {
       hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), 1, (unsigned)W), dim3(64), 0,
                          ctx->stream, (const XYZZ<F>*)partial, Bp, (uint32_t)chunks,
-                         (uint32_t)chunks, wsum, chunks * Bp, Bp);
+                         (uint32_t)chunks, wsum, chunks * Bp, Bp, (const XYZZ<F>*)nullptr);
     }
     if (!wsum_out) {
       HornerArgs<F> ha{};
@@ -1220,13 +1383,15 @@ int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
   if (ngroups > 1) {
     XYZZ<F>* mid = (XYZZ<F>*)partial + chunks * Bp;
     hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), ngroups), dim3(64), 0,
-                       ctx->stream, (const XYZZ<F>*)partial, Bp, (uint32_t)chunks, group, mid, (size_t)0, (size_t)0);
+                       ctx->stream, (const XYZZ<F>*)partial, Bp, (uint32_t)chunks, group, mid, (size_t)0, (size_t)0,
+                       (const XYZZ<F>*)nullptr);
     hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), 1), dim3(64), 0, ctx->stream,
-                       (const XYZZ<F>*)mid, Bp, ngroups, ngroups, out, (size_t)0, (size_t)0);
+                       (const XYZZ<F>*)mid, Bp, ngroups, ngroups, out, (size_t)0, (size_t)0,
+                       (const XYZZ<F>*)nullptr);
   } else {
     hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), 1), dim3(64), 0, ctx->stream,
                        (const XYZZ<F>*)partial, Bp, (uint32_t)chunks, (uint32_t)chunks, out, (size_t)0,
-                       (size_t)0);
+                       (size_t)0, (const XYZZ<F>*)nullptr);
   }
   ZK_HIP(hipGetLastError());
   return ZKMI_OK;
@@ -1237,10 +1402,10 @@ template int build_comb<Fq2>(zkmi_ctx*, const Affine<Fq2>*, size_t, const WinPla
                              int*, Affine<Fq2>*);
 template int build_impl<Fq2>(zkmi_ctx*, const Affine<Fq2>*, size_t, const WinPlan&, Affine<Fq2>*);
 template int run_impl<Fq2>(zkmi_ctx*, const zkmi_msm_bases*, const Fr*, const uint32_t*, size_t,
-                           XYZZ<Fq2>*, bool, XYZZ<Fq2>*, hipStream_t);
+                           size_t, XYZZ<Fq2>*, bool, XYZZ<Fq2>*, hipStream_t);
 #else
 extern template int run_impl<Fq2>(zkmi_ctx*, const zkmi_msm_bases*, const Fr*, const uint32_t*,
-                                  size_t, XYZZ<Fq2>*, bool, XYZZ<Fq2>*, hipStream_t);
+                                  size_t, size_t, XYZZ<Fq2>*, bool, XYZZ<Fq2>*, hipStream_t);
 
 __global__ void fill_inf_g1(G1XYZZ* out, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1300,7 +1465,8 @@ int msm_horner_run(zkmi_ctx* ctx, hipStream_t stream, int count,
 }
 
 int msm_run(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, const uint32_t* row_idx,
-            size_t Bp, void* out_xyzz, bool scalars_f, void* wsum_out, hipStream_t finish_stream) {
+            size_t Bp, size_t batch, void* out_xyzz, bool scalars_f, void* wsum_out,
+            hipStream_t finish_stream) {
   if (bases->n == 0 && wsum_out && (bases->plan.shared || bases->plan.comb)) {
     // deferred path: every window sum is the identity
     const size_t cnt = (size_t)bases->plan.W * Bp;
@@ -1323,10 +1489,14 @@ int msm_run(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, const
     ZK_HIP(hipGetLastError());
     return ZKMI_OK;
   }
+  if (batch == 0 || batch > Bp) {
+    ctx->err = "msm: batch must be in [1, Bp]";
+    return ZKMI_ERR_ARG;
+  }
   if (bases->group == 1)
-    return run_impl<Fq>(ctx, bases, scalars, row_idx, Bp, (G1XYZZ*)out_xyzz, scalars_f,
+    return run_impl<Fq>(ctx, bases, scalars, row_idx, Bp, batch, (G1XYZZ*)out_xyzz, scalars_f,
                         (G1XYZZ*)wsum_out, finish_stream);
-  return run_impl<Fq2>(ctx, bases, scalars, row_idx, Bp, (G2XYZZ*)out_xyzz, scalars_f,
+  return run_impl<Fq2>(ctx, bases, scalars, row_idx, Bp, batch, (G2XYZZ*)out_xyzz, scalars_f,
                        (G2XYZZ*)wsum_out, finish_stream);
 }
 

@@ -357,7 +357,8 @@ static int commit(zkmi_ctx* ctx, zkmi_plonk_pk* pk, int count, const Fr* const* 
   int rc;
   if ((rc = buf(ctx, pk->small[2], Bp * 128)) || (rc = buf(ctx, pk->small[3], Bp * 64))) return rc;
   for (int k = 0; k < count; k++) {
-    if ((rc = msm_run(ctx, pk->srs, scal[k], row_idx ? row_idx[k] : nullptr, Bp, pk->small[2].p)))
+    if ((rc = msm_run(ctx, pk->srs, scal[k], row_idx ? row_idx[k] : nullptr, Bp, batch,
+                      pk->small[2].p)))
       return rc;
     if ((rc = xyzz_to_affine(ctx, 1, pk->small[2].p, pk->small[3].p, Bp))) return rc;
     // [lane] affine -> out[(lane * count + k)]
@@ -599,7 +600,8 @@ int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const
     for (int k = 0; k < 3; k++) {
       ZK_HIP(hipMemcpyAsync(cols[k] + n * Bp, (const Fr*)pk->small[0].p + (size_t)(2 * k) * Bp,
                             2 * Bp * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-      if ((rc = msm_run(ctx, pk->lag[k], cols[k], pk->lag_rows[k], Bp, pk->small[2].p))) return rc;
+      if ((rc = msm_run(ctx, pk->lag[k], cols[k], pk->lag_rows[k], Bp, batch, pk->small[2].p)))
+        return rc;
       if ((rc = xyzz_to_affine(ctx, 1, pk->small[2].p, pk->small[3].p, Bp))) return rc;
       ZK_HIP(hipMemcpy2DAsync((char*)commits_out + (size_t)k * 64, (size_t)3 * 64, pk->small[3].p, 64,
                               64, batch, hipMemcpyDefault, ctx->stream));

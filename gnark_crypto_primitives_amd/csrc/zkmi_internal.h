@@ -286,9 +286,11 @@ WinPlan plan_comb(int k, bool signed_tables = true);
 void plan_comb_for_budget(size_t n1, size_t n2, double usable_bytes, int* k1, int* k2, bool* sg1,
                           bool* sg2, bool allow_signed = true);
 void plan_shared_for_budget(size_t n1, size_t n2, double usable_bytes, int* c1, int* c2);
+// batch = the lanes that hold real proofs (<= Bp): comb plans sum the groups whose scalars are the
+// same in all of them once per batch; the results of the padding lanes are then unspecified.
 int msm_run(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, const uint32_t* row_idx,
-            size_t Bp, void* out_xyzz, bool scalars_f = false, void* wsum_out = nullptr,
-            hipStream_t finish_stream = nullptr);
+            size_t Bp, size_t batch, void* out_xyzz, bool scalars_f = false,
+            void* wsum_out = nullptr, hipStream_t finish_stream = nullptr);
 // With wsum_out (shared-table plans only) msm_run stops at the W window sums ([W][Bp] XYZZ) and the
 // caller finishes with msm_horner_run -- 255 dependent doublings per proof, latency-bound, which
 // the prover runs on its assembly stream under the next batch's kernels.  With finish_stream the

@@ -372,7 +372,8 @@ int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const 
  * pointwise), [2] G1 MSMs, [3] G2 MSM, [4] assembly (third stream; overlaps the next batch's
  * quotient when one is submitted), [5] main-stream span = [1] + [2] + [3] + delta multiples,
  * [6] sum over the four G1 msm_accumulate launches alone (one event pair around each launch),
- * [7] the G2 msm_accumulate launch alone. */
+ * [7] the G2 msm_accumulate launch alone.  With comb tables a pair also brackets the launch that
+ * sums the groups whose scalars the whole batch shares, so it covers every mixed addition. */
 int zkmi_last_timings(zkmi_ctx* ctx, double* ms_out /* 8 doubles */);
 
 #ifdef __cplusplus
