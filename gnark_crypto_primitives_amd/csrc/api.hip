@@ -561,7 +561,6 @@ static WinPlan plan_explicit(int wb) {
          : wb >= 100 ? plan_shared(wb - 100)
                      : plan_uniform(wb);
 }
-static const int COMB_WINDOWS = 254;
 // HBM the prover needs beside the tables to prove batches of up to `max_batch` with a key of this
 // shape: two pipeline sets (value file, a, b, c, staged inputs, sums, commitment
 // buffers), the NTT scratch, the MSM integer scalars + digits + two partial-sum buffers, the
@@ -622,7 +621,7 @@ int zkmi_msm_bases_load(zkmi_ctx* ctx, int group, const void* bases, size_t n, i
       bool s1, s2;
       plan_comb_for_budget(group == 1 ? n : 0, group == 2 ? n : 0, 0.9 * usable, &k1, &k2, &s1, &s2);
       const int k = group == 1 ? k1 : k2;
-      if ((double)COMB_WINDOWS / k < (double)plan.W) plan = plan_comb(k, group == 1 ? s1 : s2);
+      if ((double)COMB_W / k < (double)plan.W) plan = plan_comb(k, group == 1 ? s1 : s2);
     }
   }
   return bases_load_plan(ctx, group, sb.dev, n, plan, window_bits == 0, out);
@@ -875,8 +874,8 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
     bool s1 = true, s2 = true;
     plan_comb_for_budget(auto1 ? n1 : 0, auto2 ? d->n_b : 0, 0.98 * usable, &k1, &k2, &s1, &s2,
                          d->sparse_witness == 0);
-    if (auto1 && (double)COMB_WINDOWS / k1 < (double)p1.W) p1 = plan_comb(k1, s1);
-    if (auto2 && (double)COMB_WINDOWS / k2 < (double)p2.W) p2 = plan_comb(k2, s2);
+    if (auto1 && (double)COMB_W / k1 < (double)p1.W) p1 = plan_comb(k1, s1);
+    if (auto2 && (double)COMB_W / k2 < (double)p2.W) p2 = plan_comb(k2, s2);
   }
   // sparse_witness = 2: (almost) every wire is a bit.  The wire MSMs then execute one addition per
   // group (window 0) whatever the group size, so they get small subset-sum tables and the dense

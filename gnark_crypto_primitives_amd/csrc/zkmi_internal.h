@@ -143,7 +143,10 @@ struct zkmi_msm_bases {
   int group = 1;        // 1 = G1, 2 = G2
   size_t n = 0;         // number of bases
   WinPlan plan;
-  void* table = nullptr;  // affine entries [(i * W + j) << (c-1) | (d-1)]
+  // affine entries in the 2^261 domain.  Per-window plan: d * 2^(shift_j) * P_i at
+  // i * per_base + off_j + (d - 1); shared: d * P_i at i * per_base + (d - 1); comb: entry m of
+  // group g at g * 2^k + m (2^(k-1) for sign-pattern tables)
+  void* table = nullptr;
   size_t table_bytes = 0;
   uint8_t* inf = nullptr;  // device, n flags: base i is the point at infinity (skipped)
   size_t n_groups = 0;     // comb plans: ceil(n / k)
@@ -271,36 +274,41 @@ int pointwise_h(zkmi_ctx* ctx, const NttPlan* plan, const Fr* a, const Fr* b, co
 int compute_h_bi(zkmi_ctx* ctx, const NttPlan* plan, Fr* a, Fr* b, Fr* c, Fr* t0, size_t Bp,
                  size_t n_valid, Fr** h_out, bool abc_f = false);
 
-// msm.hip
-// smallest number of windows whose table for n_total bases fits `budget_bytes`
-WinPlan plan_windows_for_budget(size_t n_total, int group, double budget_bytes);
-WinPlan plan_uniform(int c);
+// msm.hip (the templates behind these are in msm_impl.h)
+constexpr int COMB_W = 254;   // one-bit windows of a comb plan: scalars are below 2^254
+// window plans: per-window tables (of W windows; of c-bit windows), one shared table of c-bit
+// windows, comb tables over groups of k bases
 WinPlan plan_with_windows(int W);
+WinPlan plan_uniform(int c);
+WinPlan plan_shared(int c);
+WinPlan plan_comb(int k, bool signed_tables = true);
+// smallest number of windows whose per-window tables for n_total bases fit `budget_bytes`
+WinPlan plan_windows_for_budget(size_t n_total, int group, double budget_bytes);
+// comb group sizes / shared-table widths of a key's G1 and G2 bases whose tables fit `usable_bytes`
+void plan_comb_for_budget(size_t n1, size_t n2, double usable_bytes, int* k1, int* k2, bool* sg1,
+                          bool* sg2, bool allow_signed = true);
+void plan_shared_for_budget(size_t n1, size_t n2, double usable_bytes, int* c1, int* c2);
 int msm_bases_build(zkmi_ctx* ctx, int group, const void* bases_dev, size_t n, const WinPlan& plan,
                     zkmi_msm_bases** out);
 // scalars batch-inner: element (row, b) at scalars[row * Bp + b]; row_idx (device, may be null)
 // maps base i to its scalar row.  out_xyzz: Bp accumulators.
 // scalars_f: the scalars are in the F domain (solver output) instead of gnark's image
-WinPlan plan_shared(int c);
-WinPlan plan_comb(int k, bool signed_tables = true);
-void plan_comb_for_budget(size_t n1, size_t n2, double usable_bytes, int* k1, int* k2, bool* sg1,
-                          bool* sg2, bool allow_signed = true);
-void plan_shared_for_budget(size_t n1, size_t n2, double usable_bytes, int* c1, int* c2);
 // batch = the lanes that hold real proofs (<= Bp): comb plans sum the groups whose scalars are the
 // same in all of them once per batch; the results of the padding lanes are then unspecified.
+// With wsum_out (shared-table and comb plans only) msm_run stops at the W window sums ([W][Bp] XYZZ)
+// and the caller finishes with msm_horner_run -- 255 dependent doublings per proof, latency-bound,
+// which the prover runs on its assembly stream under the next batch's kernels.  With finish_stream
+// (comb plans) the sums over the chunk partials run there too (ordered after the accumulate launch
+// by an event; the partials of consecutive MSMs alternate between two buffers), so the main stream
+// holds nothing but the digit pass and the accumulate kernel.
 int msm_run(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, const uint32_t* row_idx,
             size_t Bp, size_t batch, void* out_xyzz, bool scalars_f = false,
             void* wsum_out = nullptr, hipStream_t finish_stream = nullptr);
-// With wsum_out (shared-table plans only) msm_run stops at the W window sums ([W][Bp] XYZZ) and the
-// caller finishes with msm_horner_run -- 255 dependent doublings per proof, latency-bound, which
-// the prover runs on its assembly stream under the next batch's kernels.  With finish_stream the
-// sums over the chunk partials run there too (ordered after the accumulate launch by an event; the
-// partials of consecutive MSMs alternate between two buffers), so the main stream holds nothing
-// but the digit pass and the accumulate kernel.
+// Horner step of up to four deferred MSMs of one group (same plan) in one launch on `stream`
 int msm_horner_run(zkmi_ctx* ctx, hipStream_t stream, int count,
                    const zkmi_msm_bases* const* bases, void* const* wsums, void* const* outs,
                    size_t Bp);
-
+// XYZZ -> affine, n points of `group`
 int xyzz_to_affine(zkmi_ctx* ctx, int group, const void* in, void* out, size_t n);
 
 // solve.hip
