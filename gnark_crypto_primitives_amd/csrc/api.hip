@@ -387,16 +387,7 @@ void zkmi_destroy(zkmi_ctx* ctx) {
   }
   hipStreamDestroy(ctx->stream2);
   hipStreamDestroy(ctx->stream3);
-  for (auto& p : ctx->plans) {
-    hipFree(p.tw_fwd);
-    hipFree(p.tw_inv);
-    hipFree(p.coset_fwd);
-    hipFree(p.coset_inv);
-    hipFree(p.tw29_fwd);
-    hipFree(p.tw29_inv);
-    hipFree(p.coset29_fwd);
-    hipFree(p.coset29n_fwd);
-  }
+  for (auto& p : ctx->plans) free_plan(p);
   for (auto& st : ctx->sets)
     for (DevBuf* b : {&st.slots, &st.a, &st.b, &st.c, &st.misc, &st.sums, &st.commit})
       if (b->p) hipFree(b->p);

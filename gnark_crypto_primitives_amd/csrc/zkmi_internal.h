@@ -27,22 +27,26 @@ struct DevBuf {
   size_t bytes = 0;
 };
 
+// Constants of the domain of size n = 2^log_n (w its generator, g = 5 the coset shift), built by
+// get_plan and freed by free_plan (ntt.hip).  Each is named with the kernel argument it feeds.
 struct NttPlan {
   int log_n = 0;
-  Fr* tw_fwd = nullptr;     // n/2 powers of w
-  Fr* tw_inv = nullptr;     // n/2 powers of w^-1
-  Fr* coset_fwd = nullptr;  // g^i, n
-  Fr* coset_inv = nullptr;  // g^-i / n, n
-  Fr n_inv;                 // 1/n
-  Fr den;                   // 1/(g^n - 1)
-  // the same constants in the 2^261 Montgomery domain of ff29.h (canonical, packed 8 x u32)
-  Fr* tw29_fwd = nullptr;
-  Fr* tw29_inv = nullptr;
-  Fr* coset29_fwd = nullptr;
-  Fr* coset29n_fwd = nullptr;  // g^i / n (F domain): scaling between a fused iNTT -> coset NTT
-  Fr n_inv29;
-  Fr den29;
-  Fr ninv_den;  // den / n in gnark's image: uniform post factor of the quotient's c transform
+  // gnark's image (x * 2^256, ff.h).  Device tables:
+  Fr* tw_fwd = nullptr;     // w^i, i < n/2: `tw` of the ff.h passes, forward
+  Fr* tw_inv = nullptr;     // w^-i, i < n/2: `tw`, inverse
+  Fr* coset_fwd = nullptr;  // g^i, i < n: `pre` of a forward coset transform on the ff.h passes
+  Fr* coset_inv = nullptr;  // g^-i / n, i < n: `post` of inverse coset transform, ff.h and 29-bit
+  // and factors passed by value:
+  Fr n_inv;                 // 1/n: `post_uniform` of an inverse transform, ff.h and 29-bit
+  Fr den;                   // 1/(g^n - 1): `den` of pointwise_h_kernel
+  Fr ninv_den;              // den / n: `post_uniform` of the quotient's transform of c
+  // The F domain (x * 2^261, canonical, packed 8 x u32: ff29.h).  Device tables:
+  Fr* tw29_fwd = nullptr;      // w^i: `tw` of the 29-bit passes, `tw_fwd` of the fused pass
+  Fr* tw29_inv = nullptr;      // w^-i: `tw` of the 29-bit passes, `tw_inv` of the fused pass
+  Fr* coset29_fwd = nullptr;   // g^i: `pre` of a forward coset transform on the 29-bit passes
+  Fr* coset29n_fwd = nullptr;  // g^i / n: `scale` of the fused pass (inverse -> coset forward)
+  // and a factor passed by value:
+  Fr den29;                 // 1/(g^n - 1): `den29` of pointwise_h29_kernel
 };
 
 }  // namespace zk
@@ -263,12 +267,10 @@ int transpose_out(zkmi_ctx* ctx, const void* src_bi, void* dst_pm, size_t rows, 
 
 // ntt.hip
 int get_plan(zkmi_ctx* ctx, int log_n, NttPlan** out);
+void free_plan(NttPlan& p);   // the plan's device tables
 // src -> dst (distinct buffers), batch-inner [n][Bp]; rows >= n_valid of src are read as zero
 int ntt_bi(zkmi_ctx* ctx, const NttPlan* plan, const Fr* src, Fr* dst, size_t Bp, bool inverse,
            bool coset, size_t n_valid);
-// h = (a*b - c) * den, elementwise over n*Bp
-int pointwise_h(zkmi_ctx* ctx, const NttPlan* plan, const Fr* a, const Fr* b, const Fr* c, Fr* h,
-                size_t Bp);
 // full quotient: a,b,c batch-inner [n][Bp] (rows >= n_valid zero) -> h in `a_out`; t0,t1 scratch
 // abc_f: a, b, c are in the F domain (solver output); the result h is always in gnark's image
 int compute_h_bi(zkmi_ctx* ctx, const NttPlan* plan, Fr* a, Fr* b, Fr* c, Fr* t0, size_t Bp,

@@ -29,7 +29,7 @@ def test_field_mul(zk_ctx, cref, which):
     assert np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("log_n", [1, 2, 3, 4, 5, 8, 9, 13])
+@pytest.mark.parametrize("log_n", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13])
 @pytest.mark.parametrize("inverse,coset", [(0, 0), (1, 0), (0, 1), (1, 1)])
 def test_ntt(zk_ctx, cref, log_n, inverse, coset):
     r = H.rng(100 + log_n)
@@ -42,7 +42,7 @@ def test_ntt(zk_ctx, cref, log_n, inverse, coset):
     assert np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("log_n", [3, 4, 8, 9, 10, 11, 12, 13, 14, 15])
+@pytest.mark.parametrize("log_n", [3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15])
 def test_h(zk_ctx, cref, log_n):
     r = H.rng(200 + log_n)
     n = 1 << log_n
