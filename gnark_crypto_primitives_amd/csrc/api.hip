@@ -952,183 +952,17 @@ void zkmi_cs_free(zkmi_ctx* ctx, zkmi_cs* cs) {
 int zkmi_cs_load(zkmi_ctx* ctx, const zkmi_cs_desc* d, zkmi_cs** out) {
   ZK_HIP(hipSetDevice(ctx->device));
   if (!d || !out) return ZKMI_ERR_ARG;
-  const uint32_t S = d->lanes_per_proof;
-  if (S == 0 || S > 64 || (S & (S - 1))) {
-    ctx->err = "cs: lanes_per_proof must be a power of two, 1 .. 64";
-    return ZKMI_ERR_ARG;
-  }
-  // validate every slot / constant / row index on the host before anything reaches a kernel
-  enum { CLS_M = 1, CLS_X, CLS_A, CLS_R, CLS_I, CLS_BITS, CLS_BINV, CLS_HIST, CLS_COMMIT, CLS_EMUL = 11,
-         CLS_LIMBS = 12 };
-  enum { OP_HIST = 20, OP_HQ = 21, OP_COMMIT = 22, OP_BXOR = 23, OP_BAND = 24, OP_EMUL = 25 };
-  std::vector<std::pair<uint32_t, uint32_t>> commit_rows;
-  bool has_emul = false;
-  const uint32_t* p = d->program;
-  const size_t stride = (size_t)(1 + S) * 4;
-  std::vector<uint8_t> row_seen(d->n_constraints, 0);
-  uint32_t n_abc = 0;
-  auto bad = [&](uint32_t r) {
-    ctx->err = "cs: malformed program row " + std::to_string(r);
-    return ZKMI_ERR_ARG;
-  };
-  for (uint32_t r = 0; r < d->n_rows; r++) {
-    const uint32_t* h = p + r * stride;
-    const uint32_t cls = h[0] & 0xff;
-    if (h[0] & 0x100) return bad(r);   // a pair row outside a BATCHINV step
-    if (cls == CLS_BINV) {
-      const uint32_t npairs = h[1], nrows = h[2];
-      if ((uint64_t)r + nrows >= (uint64_t)d->n_rows + 0 && nrows) {
-        if ((uint64_t)r + nrows > d->n_rows - 1) return bad(r);
-      }
-      if (nrows != (npairs + S - 1) / S) return bad(r);
-      std::vector<uint32_t> dsts, srcs;
-      for (uint32_t t = 1; t <= nrows; t++) {
-        const uint32_t* hh = p + (size_t)(r + t) * stride;
-        if (hh[0] != (CLS_BINV | 0x100u)) return bad(r + t);
-        for (uint32_t l = 0; l < S; l++) {
-          const uint32_t* q = hh + 4 * (1 + l);
-          if ((q[0] & 0x1f) == OP_END) continue;
-          if ((q[0] & 0x1f) != OP_PAIR || q[1] >= d->n_slots || q[2] >= d->n_slots || q[1] == q[2])
-            return bad(r + t);
-          dsts.push_back(q[1]);
-          srcs.push_back(q[2]);
-        }
-      }
-      if (dsts.size() != npairs) return bad(r);
-      std::sort(srcs.begin(), srcs.end());
-      for (uint32_t x : dsts)   // no dst aliases any src (dst rows are the prefix scratch)
-        if (std::binary_search(srcs.begin(), srcs.end(), x)) return bad(r);
-      r += nrows;
-      continue;
-    }
-    if (cls == CLS_HIST || cls == CLS_EMUL) {
-      // header (class, n queries, n rows, table size), quad 0 = (OP_HIST, first counter wire);
-      // the rows that follow hold the query slots; every quad carries class 0.
-      // CLS_EMUL: header (class, na + nb, n rows, aux), quad 0 = (OP_EMUL, first wire, 0, aux),
-      // aux = nout | na << 8 | first modulus constant << 12; rows: the limb slots of a, then of b
-      const uint32_t nq = h[1], nrows = h[2], size = h[3];
-      const uint32_t* q0 = h + 4;
-      if (nrows != (nq + S - 1) / S || (uint64_t)r + nrows > (uint64_t)d->n_rows - 1) return bad(r);
-      if (cls == CLS_HIST) {
-        if (q0[0] != OP_HIST || size == 0 || (uint64_t)q0[1] + size > d->n_wires) return bad(r);
-      } else {
-        const uint32_t nout = size & 0xff, na = (size >> 8) & 0xf, c0 = size >> 12;
-        if (q0[0] != OP_EMUL || q0[3] != size || nout < 5 || nout > 12 || na < 1 || na > 4 ||
-            nq <= na || nq - na > 4 || (uint64_t)q0[1] + nout > d->n_wires ||
-            (uint64_t)c0 + 4 > d->n_consts)
-          return bad(r);
-        has_emul = true;
-      }
-      for (uint32_t l = 1; l < S; l++)
-        if (h[4 * (1 + l)] != 0) return bad(r);
-      uint32_t seen = 0;
-      for (uint32_t t = 1; t <= nrows; t++) {
-        const uint32_t* hh = p + (size_t)(r + t) * stride;
-        if (hh[0] != (cls | 0x100u)) return bad(r + t);
-        for (uint32_t l = 0; l < S; l++) {
-          const uint32_t* q = hh + 4 * (1 + l);
-          if (q[0] == OP_END) {
-            if (seen < nq && (t - 1) * S + l < nq) return bad(r + t);
-            continue;
-          }
-          if (q[0] != OP_HQ || q[2] >= d->n_slots || (t - 1) * S + l != seen) return bad(r + t);
-          seen++;
-        }
-      }
-      if (seen != nq) return bad(r);
-      r += nrows;
-      continue;
-    }
-    if (cls == CLS_COMMIT) {
-      // one row: header (class, n operands, 0, commitment index), quad 0 = (OP_COMMIT, wire, 0, index)
-      const uint32_t* q0 = h + 4;
-      if (q0[0] != OP_COMMIT || q0[1] >= d->n_wires || h[3] != commit_rows.size() || q0[3] != h[3])
-        return bad(r);
-      for (uint32_t l = 1; l < S; l++)
-        if (h[4 * (1 + l)] != 0) return bad(r);
-      commit_rows.emplace_back(r, q0[1]);
-      continue;
-    }
-    if (cls == CLS_LIMBS) {
-      // up to S short decompositions: quads (OP_BITS, first wire, source slot, count | width << 16)
-      // with class bits 0, idle quads all zero
-      bool any = false;
-      for (uint32_t l = 0; l < S; l++) {
-        const uint32_t* q = h + 4 * (1 + l);
-        if (q[0] == 0 && q[1] == 0 && q[2] == 0 && q[3] == 0) {
-          if (l == 0) return bad(r);   // the step's class is read from quad 0
-          continue;
-        }
-        const uint32_t n = q[3] & 0xffffu, wd = q[3] >> 16;
-        if (q[0] != OP_BITS || n == 0 || n > 16 || wd > 16 || q[2] >= d->n_slots ||
-            (uint64_t)q[1] + n > d->n_slots)
-          return bad(r);
-        any = true;
-      }
-      if (!any) return bad(r);
-      continue;
-    }
-    if (cls < CLS_M || cls > CLS_BITS) return bad(r);
-    for (uint32_t l = 0; l < S; l++) {
-      const uint32_t* q = h + 4 * (1 + l);
-      const uint32_t op = q[0] & 0x1f, k = q[0] >> 9, dst = q[1], a = q[2], b = q[3];
-      if (((q[0] >> 6) & 7u) != cls) return bad(r);   // every quad carries its step's class
-      if (op == OP_END) continue;
-      bool ok = false, emits = false;
-      switch (cls) {
-        case CLS_M:
-          emits = op == OP_MULABC;
-          ok = (op == OP_MUL || op == OP_MULABC) ? (dst < d->n_slots && a < d->n_slots && b < d->n_slots)
-               : op == OP_MULC                   ? (dst < d->n_slots && a < d->n_slots && b < d->n_consts)
-               : op == OP_FMA  ? (dst < d->n_slots && a < d->n_slots && b < d->n_slots && k < d->n_slots)
-               : op == OP_FMAC ? (dst < d->n_slots && a < d->n_slots && b < d->n_consts && k < d->n_slots)
-                               : false;
-          break;
-        case CLS_X:
-          emits = op == OP_XORABC;
-          ok = (op == OP_XORABC || op == OP_XOR) && dst < d->n_slots && a < d->n_slots &&
-               b < d->n_slots;
-          break;
-        case CLS_A:
-          ok = (op == OP_ADD || op == OP_SUB) ? (dst < d->n_slots && a < d->n_slots && b < d->n_slots)
-               : op == OP_ADDC                ? (dst < d->n_slots && a < d->n_slots && b < d->n_consts)
-               : (op == OP_NEG || op == OP_COPY) ? (dst < d->n_slots && a < d->n_slots)
-               : op == OP_SETC                   ? (dst < d->n_slots && b < d->n_consts)
-                                                 : false;
-          break;
-        case CLS_R:
-          emits = true;
-          ok = op == OP_ABC && dst < d->n_slots && a < d->n_slots && b < d->n_slots;
-          break;
-        case CLS_I:
-          ok = op == OP_INV   ? (dst < d->n_slots && a < d->n_slots)
-               : (op == OP_DIV || op == OP_BXOR || op == OP_BAND)
-                   ? (dst < d->n_slots && a < d->n_slots && b < d->n_slots)
-                   : false;
-          break;
-        case CLS_BITS:
-          // b = count | width << 16: count limbs of width bits (width 0 / 1: bits)
-          ok = l == 0 && op == OP_BITS && a < d->n_slots && (b >> 16) <= 16 && (b & 0xffffu) <= 256 &&
-               (uint64_t)(b & 0xffffu) * ((b >> 16) ? (b >> 16) : 1u) <= 256 &&
-               (uint64_t)dst + (b & 0xffffu) <= d->n_slots;
-          break;
-      }
-      if (ok && emits) {
-        ok = k < d->n_constraints && !row_seen[k];
-        if (ok) {
-          row_seen[k] = 1;
-          n_abc++;
-        }
-      }
-      if (!ok) return bad(r);
-    }
-  }
-  if (n_abc != d->n_constraints) {
-    ctx->err = "cs: program emits " + std::to_string(n_abc) + " constraint rows, expected " +
-               std::to_string(d->n_constraints);
-    return ZKMI_ERR_ARG;
-  }
   auto* cs = new zkmi_cs();
+  // every slot / constant / row index is checked on the host before anything reaches a kernel
+  const std::string err =
+      vprog_validate({d->n_wires, d->n_slots, d->n_consts, d->n_constraints, d->n_rows,
+                      d->lanes_per_proof},
+                     d->program, &cs->commit_rows, &cs->has_emul);
+  if (!err.empty()) {
+    delete cs;
+    ctx->err = err;
+    return ZKMI_ERR_ARG;
+  }
   cs->n_wires = d->n_wires;
   cs->n_public = d->n_public;
   cs->n_secret = d->n_secret;
@@ -1136,10 +970,9 @@ int zkmi_cs_load(zkmi_ctx* ctx, const zkmi_cs_desc* d, zkmi_cs** out) {
   cs->n_slots = d->n_slots;
   cs->n_rows = d->n_rows;
   cs->n_consts = d->n_consts;
-  cs->lanes_per_proof = S;
-  cs->commit_rows = commit_rows;   // (row, commitment wire) in commitment order
-  cs->has_emul = has_emul;
-  int rc = upload_u32(ctx, d->program, (size_t)d->n_rows * stride, &cs->program);
+  cs->lanes_per_proof = d->lanes_per_proof;
+  int rc = upload_u32(ctx, d->program, (size_t)d->n_rows * (1 + d->lanes_per_proof) * 4,
+                      &cs->program);
   if (rc) {
     delete cs;
     return rc;

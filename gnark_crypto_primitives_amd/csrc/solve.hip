@@ -16,7 +16,7 @@
 //     (the two shapes almost every constraint of the gadget circuits has): one op, two loads.
 //   * OP_ABC copies the three operand values of constraint k into the quotient inputs a, b, c,
 //     and for assertion-type constraints checks a*b == c (per-proof status).
-// Opcodes: frontend/api.py.
+// The program format (opcodes, classes, row layouts): vprog.h.
 //
 // Value domain.  88 % of the solver's issue slots are field products (96 872 per proof at
 // Arbo-160).  The value file therefore holds x * 2^261 mod r (canonical, packed 8 x u32: the "F
@@ -71,6 +71,21 @@ __device__ __forceinline__ Fr f_plain(const Fr& a) {  // x * 2^261 -> x as a pla
   pack_canonical<Fr29Params>(r.v, mul(unpack29<Fr29Params>(a.v), o));
   return r;
 }
+// the F-domain image of a plain integer below 2^64: one F-domain product (. 2^-261) by 2^522
+__device__ __forceinline__ Fr f_small(uint32_t lo, uint32_t hi = 0) {
+  Fr m = Fr::zero();
+  m.v[0] = lo;
+  m.v[1] = hi;
+  return fmul(m, Fr{{0x45b69bd4u, 0x38c2e14bu, 0x85883377u, 0x0ffedb18u,   // c522 = 2^522 mod r
+                     0xabc6e54du, 0x7840f9f0u, 0x848b0f05u, 0x0a054a3eu}});
+}
+// bits [pos, pos + wd) of the 256-bit integer v, wd <= 16; the bits above 255 are 0
+__device__ __forceinline__ uint32_t limb_at(const Fr& v, uint32_t pos, uint32_t wd) {
+  if (pos >= 256) return 0;
+  const uint32_t lo = v.v[pos >> 5], hi = (pos >> 5) < 7 ? v.v[(pos >> 5) + 1] : 0u;
+  const uint64_t two = ((uint64_t)hi << 32) | lo;
+  return (uint32_t)(two >> (pos & 31)) & ((1u << wd) - 1u);
+}
 
 // ---- VLIW solver: S sub-lanes of a wavefront per proof -----------------------------------------
 // The frontend packs independent operations of one class into steps (frontend/schedule.py); a
@@ -85,12 +100,6 @@ __device__ __forceinline__ Fr f_plain(const Fr& a) {  // x * 2^261 -> x as a pla
 // instruction, because the vector memory instructions of a wavefront reach the CU's L1 / the L2 in
 // issue order (a workgroup-scope fence here -- s_waitcnt vmcnt(0) after every step -- exposed the
 // store latency: 96 -> 7x ms per batch).
-enum { CLS_M = 1, CLS_X, CLS_A, CLS_R, CLS_I, CLS_BITS, CLS_BINV, CLS_HIST, CLS_COMMIT, CLS_B_UNUSED,
-       CLS_EMUL, CLS_LIMBS };
-// CLS_HIST / CLS_COMMIT do not fit the three class bits of an operand quad: their quads carry
-// class 0 and the class sits in the header quad.  OP_HIST = 20, OP_HQ = 21, OP_COMMIT = 22
-// (frontend/api.py).
-enum { OP_HIST = 20, OP_HQ = 21, OP_COMMIT = 22, OP_BXOR = 23, OP_BAND = 24, OP_EMUL = 25 };
 
 // Stores of the hot step classes.  gfx950 reads the data registers of a vector store out of order
 // with later VGPR writes, so the compiler waits for a store to complete (s_waitcnt vmcnt) before it
@@ -105,26 +114,22 @@ template <int BANK, bool WAIT, bool NT>
 __device__ __forceinline__ void st_acc(Fr* base, size_t row, size_t b, size_t Bp, const Fr& x) {
   uint4* p0 = reinterpret_cast<uint4*>(base) + row * 2 * Bp + b;
   uint4* p1 = p0 + Bp;
+#define ZK_ST_ACC_ASM(A0, A1, A2, A3, A4, A5, A6, A7, LO, HI, NT_)                                 \
+  asm volatile("v_accvgpr_write_b32 " A0 ", %2\n v_accvgpr_write_b32 " A1 ", %3\n"                 \
+               "v_accvgpr_write_b32 " A2 ", %4\n v_accvgpr_write_b32 " A3 ", %5\n"                 \
+               "v_accvgpr_write_b32 " A4 ", %6\n v_accvgpr_write_b32 " A5 ", %7\n"                 \
+               "v_accvgpr_write_b32 " A6 ", %8\n v_accvgpr_write_b32 " A7 ", %9\n s_nop 1\n"       \
+               "global_store_dwordx4 %0, " LO ", off" NT_ "\n"                                      \
+               " global_store_dwordx4 %1, " HI ", off" NT_                                         \
+               :: "v"(p0), "v"(p1), "v"(x.v[0]), "v"(x.v[1]), "v"(x.v[2]), "v"(x.v[3]),            \
+                  "v"(x.v[4]), "v"(x.v[5]), "v"(x.v[6]), "v"(x.v[7])                               \
+               : A0, A1, A2, A3, A4, A5, A6, A7, "memory")
 #define ZK_ST_ACC(A0, A1, A2, A3, A4, A5, A6, A7, LO, HI)                                         \
   if (WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                       \
-  if (NT)                                                                                          \
-    asm volatile("v_accvgpr_write_b32 " A0 ", %2\n v_accvgpr_write_b32 " A1 ", %3\n"               \
-                 "v_accvgpr_write_b32 " A2 ", %4\n v_accvgpr_write_b32 " A3 ", %5\n"               \
-                 "v_accvgpr_write_b32 " A4 ", %6\n v_accvgpr_write_b32 " A5 ", %7\n"               \
-                 "v_accvgpr_write_b32 " A6 ", %8\n v_accvgpr_write_b32 " A7 ", %9\n s_nop 1\n"     \
-                 "global_store_dwordx4 %0, " LO ", off nt\n global_store_dwordx4 %1, " HI ", off nt" \
-                 :: "v"(p0), "v"(p1), "v"(x.v[0]), "v"(x.v[1]), "v"(x.v[2]), "v"(x.v[3]),          \
-                    "v"(x.v[4]), "v"(x.v[5]), "v"(x.v[6]), "v"(x.v[7])                             \
-                 : A0, A1, A2, A3, A4, A5, A6, A7, "memory");                                      \
+  if constexpr (NT)                                                                                \
+    ZK_ST_ACC_ASM(A0, A1, A2, A3, A4, A5, A6, A7, LO, HI, " nt");                                  \
   else                                                                                             \
-    asm volatile("v_accvgpr_write_b32 " A0 ", %2\n v_accvgpr_write_b32 " A1 ", %3\n"               \
-                 "v_accvgpr_write_b32 " A2 ", %4\n v_accvgpr_write_b32 " A3 ", %5\n"               \
-                 "v_accvgpr_write_b32 " A4 ", %6\n v_accvgpr_write_b32 " A5 ", %7\n"               \
-                 "v_accvgpr_write_b32 " A6 ", %8\n v_accvgpr_write_b32 " A7 ", %9\n s_nop 1\n"     \
-                 "global_store_dwordx4 %0, " LO ", off\n global_store_dwordx4 %1, " HI ", off"      \
-                 :: "v"(p0), "v"(p1), "v"(x.v[0]), "v"(x.v[1]), "v"(x.v[2]), "v"(x.v[3]),          \
-                    "v"(x.v[4]), "v"(x.v[5]), "v"(x.v[6]), "v"(x.v[7])                             \
-                 : A0, A1, A2, A3, A4, A5, A6, A7, "memory")
+    ZK_ST_ACC_ASM(A0, A1, A2, A3, A4, A5, A6, A7, LO, HI, "")
   if (BANK == 0) {
     ZK_ST_ACC("a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a[0:3]", "a[4:7]");
   } else if (BANK == 1) {
@@ -135,6 +140,7 @@ __device__ __forceinline__ void st_acc(Fr* base, size_t row, size_t b, size_t Bp
     ZK_ST_ACC("a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", "a[24:27]", "a[28:31]");
   }
 #undef ZK_ST_ACC
+#undef ZK_ST_ACC_ASM
 }
 
 // value-file slot i of this proof, or constant i: one pair of loads from a per-lane address
@@ -207,8 +213,8 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
     const uint4 q = pq[(r - ci * CH) * RQ + 1 + sl];
     // the step's class rides in every operand quad (also the idle ones): no dependent scalar load
     // of the header on the critical path
-    const uint32_t cls = __builtin_amdgcn_readfirstlane((q.x >> 6) & 7u);
-    const uint32_t op = q.x & 0x1fu, k = q.x >> 9;
+    const uint32_t cls = __builtin_amdgcn_readfirstlane(vq_cls(q.x));
+    const uint32_t op = vq_op(q.x), k = vq_k(q.x);
     const uint32_t d = q.y, x = q.z, y = q.w;
     switch (cls) {
       case CLS_M:
@@ -270,7 +276,7 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
           st_acc<1, true, true>(a, k, lane, Bp, va);
           st_acc<2, false, true>(b, k, lane, Bp, vb);
           st_acc<3, false, true>(c, k, lane, Bp, vc);
-          if ((q.x & 0x20u) && fmul(va, vb) != vc) st = ZKMI_ERR_UNSATISFIED;
+          if (vq_assert(q.x) && fmul(va, vb) != vc) st = ZKMI_ERR_UNSATISFIED;
         }
         break;
       case CLS_I:
@@ -278,26 +284,18 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
         // wave-uniform up to idle sub-lanes
         if (op == OP_BXOR || op == OP_BAND) {
           // byte-op hints of the lookup tables: both operands as plain integers (low word), XOR / AND,
-          // back into the F domain (plain m times 2^522 through the F-domain product)
-          constexpr uint32_t c522[8] = {0x45b69bd4u, 0x38c2e14bu, 0x85883377u, 0x0ffedb18u,
-                                        0xabc6e54du, 0x7840f9f0u, 0x848b0f05u, 0x0a054a3eu};
-          Fr k522;
-#pragma unroll
-          for (int t = 0; t < 8; t++) k522.v[t] = c522[t];
+          // back into the F domain
           const Fr pa = f_plain(LD(x)), pb = f_plain(LD(y));
-          Fr pm = Fr::zero();
-          pm.v[0] = op == OP_BXOR ? (pa.v[0] ^ pb.v[0]) : (pa.v[0] & pb.v[0]);
-          STA(d, fmul(pm, k522));
+          STA(d, f_small(op == OP_BXOR ? (pa.v[0] ^ pb.v[0]) : (pa.v[0] & pb.v[0])));
         } else if (op != OP_END) {
           const Fr va = LD(x), vy = LD(op == OP_DIV ? y : x);
           STA(d, op == OP_DIV ? fmul(va, finv(vy)) : finv(va));
         }
         break;
       case CLS_BITS: {
-        // one instruction, quad of sub-lane 0: (dst0, src, n bits); the sub-lanes split the bits
-        // q0.w = count | width << 16: `count` limbs of `width` bits (width 0 / 1: bits)
+        // one instruction, quad of sub-lane 0: the sub-lanes split its limbs
         const uint4 q0 = prog[(size_t)r * (1 + S) + 1];
-        const uint32_t n = q0.w & 0xffffu, wd = __builtin_amdgcn_readfirstlane(q0.w >> 16);
+        const uint32_t n = vbits_count(q0.w), wd = __builtin_amdgcn_readfirstlane(vbits_width(q0.w));
         const uint32_t per = (n + S - 1) / S;
         const uint32_t i0 = sl * per, i1 = i0 + per < n ? i0 + per : n;
         const Fr v = f_plain(LD(q0.z));
@@ -308,25 +306,7 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
             ST(q0.y + i, bit ? one : zero);
           }
         } else {
-          // limb i = bits [i wd, (i + 1) wd) of the integer (wd <= 16), as the F-domain image of
-          // that small integer: plain m times 2^522 through the F-domain product (. 2^-261)
-          constexpr uint32_t c522[8] = {0x45b69bd4u, 0x38c2e14bu, 0x85883377u, 0x0ffedb18u,
-                                        0xabc6e54du, 0x7840f9f0u, 0x848b0f05u, 0x0a054a3eu};   // 2^522 mod r
-          Fr k522;
-#pragma unroll
-          for (int t = 0; t < 8; t++) k522.v[t] = c522[t];
-          for (uint32_t i = i0; i < i1; i++) {
-            const uint32_t pos = i * wd;
-            uint32_t m = 0;
-            if (pos < 256) {
-              const uint32_t lo = v.v[pos >> 5], hi = (pos >> 5) < 7 ? v.v[(pos >> 5) + 1] : 0u;
-              const uint64_t two = ((uint64_t)hi << 32) | lo;
-              m = (uint32_t)(two >> (pos & 31)) & ((1u << wd) - 1u);
-            }
-            Fr pm = Fr::zero();
-            pm.v[0] = m;
-            ST(q0.y + i, fmul(pm, k522));
-          }
+          for (uint32_t i = i0; i < i1; i++) ST(q0.y + i, f_small(limb_at(v, i * wd, wd)));
         }
         // compiler-visible stores: complete them here, or the register-reuse waits they force
         // (see st_acc) would reappear at the top of every following step
@@ -334,16 +314,15 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
         break;
       }
       case CLS_BINV: {
-        // hdr.y pairs in the hdr.z rows that follow, S pairs per row: every sub-lane inverts its
-        // own column of pairs with one field inversion (Montgomery's trick); dst rows double as
-        // the prefix-product scratch; dst and src slots are distinct wires
+        // every sub-lane inverts its own column of the unit's pairs with one field inversion
+        // (Montgomery's trick); dst rows double as the prefix-product scratch
         const uint4 hdr = prog[(size_t)r * (1 + S)];
         const uint32_t nrows = __builtin_amdgcn_readfirstlane(hdr.z);
         const uint4* pr = prog + (size_t)(r + 1) * (1 + S) + 1 + sl;
         Fr acc = f_one();
         for (uint32_t t = 0; t < nrows; t++) {
           const uint4 p = pr[(size_t)t * (1 + S)];
-          if ((p.x & 0x1fu) != OP_PAIR) continue;
+          if (vq_op(p.x) != OP_PAIR) continue;
           const Fr v = LD(p.z);
           ST(p.y, acc);
           if (!v.is_zero()) acc = fmul(acc, v);
@@ -351,7 +330,7 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
         Fr inv = finv(acc);
         for (uint32_t t = nrows; t-- > 0;) {
           const uint4 p = pr[(size_t)t * (1 + S)];
-          if ((p.x & 0x1fu) != OP_PAIR) continue;
+          if (vq_op(p.x) != OP_PAIR) continue;
           const Fr v = LD(p.z);
           if (v.is_zero()) {
             ST(p.y, Fr::zero());
@@ -366,19 +345,21 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
         break;
       }
       default: {
-        // class 0: the header quad names the class.  CLS_HIST: multiplicities of the table
-        // 0 .. size - 1 among hdr.y queries (the hdr.z rows that follow, S queries per row) into
-        // the consecutive wires starting at slot q0.y.  The sub-lanes zero the counters, then every
-        // sub-lane walks its own column of the query rows and counts with an atomic add on the
-        // low word of the counter's slot (the sub-lanes of a proof share the counters; a query
-        // outside the table counts nowhere), then the sub-lanes turn the integers into field
-        // elements in place.  CLS_COMMIT rows are never executed: the host ends a launch in
-        // front of them.
+        // class bits 0: the header quad names the class, and the units' own rows follow theirs.
+        // (CLS_COMMIT rows are never executed: the host ends a launch in front of them.)
         const uint4 hdr = prog[(size_t)r * (1 + S)];
-        if ((hdr.x & 0xffu) == CLS_HIST && !(hdr.x & 0x100u)) {
+        const uint32_t hw = __builtin_amdgcn_readfirstlane(hdr.x);
+        const uint32_t hcls = (hw & VH_CONT) ? 0u : vh_cls(hw);
+        const uint32_t nq = __builtin_amdgcn_readfirstlane(hdr.y);
+        const uint32_t nrows = __builtin_amdgcn_readfirstlane(hdr.z);
+        const uint32_t aux = __builtin_amdgcn_readfirstlane(hdr.w);
+        if (hcls == CLS_HIST) {
+          // The sub-lanes zero the `size` counters at slot q0.y .., then every sub-lane walks its own
+          // column of the query rows and counts with an atomic add on the low word of the
+          // counter's slot (the sub-lanes of a proof share the counters; a query outside the table
+          // counts nowhere), then the sub-lanes turn the integers into field elements in place.
           const uint4 q0 = prog[(size_t)r * (1 + S) + 1];
-          const uint32_t nrows = __builtin_amdgcn_readfirstlane(hdr.z);
-          const uint32_t size = __builtin_amdgcn_readfirstlane(hdr.w);
+          const uint32_t size = aux;
           const Fr zero = Fr::zero();
           for (uint32_t j = sl; j < size; j += S) ST(q0.y + j, zero);
           __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
@@ -386,7 +367,7 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
           const uint4* pr = prog + (size_t)(r + 1) * (1 + S) + 1 + sl;
           for (uint32_t t = 0; t < nrows; t++) {
             const uint4 p = pr[(size_t)t * (1 + S)];
-            if ((p.x & 0x1fu) != OP_HQ) continue;
+            if (vq_op(p.x) != OP_HQ) continue;
             const Fr v = f_plain(LD(p.z));
             if ((v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0 && v.v[0] < size) {
               uint32_t* cnt = reinterpret_cast<uint32_t*>(
@@ -396,61 +377,28 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
           }
           __builtin_amdgcn_s_waitcnt(0x0F70);
           __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-          constexpr uint32_t c522h[8] = {0x45b69bd4u, 0x38c2e14bu, 0x85883377u, 0x0ffedb18u,
-                                         0xabc6e54du, 0x7840f9f0u, 0x848b0f05u, 0x0a054a3eu};   // 2^522 mod r
-          Fr k522h;
-#pragma unroll
-          for (int t = 0; t < 8; t++) k522h.v[t] = c522h[t];
           for (uint32_t j = sl; j < size; j += S) {
             uint32_t* cnt = reinterpret_cast<uint32_t*>(reinterpret_cast<uint4*>(slots) +
                                                         (size_t)(q0.y + j) * 2 * Bp + lane);
-            Fr pm = Fr::zero();
-            pm.v[0] = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ST(q0.y + j, fmul(pm, k522h));
+            ST(q0.y + j, f_small(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
           }
           r += nrows;
           __builtin_amdgcn_s_waitcnt(0x0F70);
-        }
-        // CLS_LIMBS: up to S short decompositions in one step (the limb hints of the range checker:
-        // a handful of limbs each; CLS_BITS splits ONE long decomposition over the sub-lanes instead).
-        // Every sub-lane's quad is (OP_BITS, first slot, source slot, count | width << 16), count <= 16.
-        if ((hdr.x & 0xffu) == CLS_LIMBS) {
+        } else if (hcls == CLS_LIMBS) {
+          // every sub-lane's own short decomposition (the limb hints of the range checker: a handful
+          // of limbs each; CLS_BITS splits ONE long decomposition over the sub-lanes instead)
           if (op == OP_BITS) {
-            const uint32_t n = y & 0xffffu, wd = y >> 16;
+            const uint32_t n = vbits_count(y), wd = vbits_width(y) ? vbits_width(y) : 1u;
             const Fr v = f_plain(LD(x));
-            constexpr uint32_t c522l[8] = {0x45b69bd4u, 0x38c2e14bu, 0x85883377u, 0x0ffedb18u,
-                                           0xabc6e54du, 0x7840f9f0u, 0x848b0f05u, 0x0a054a3eu};   // 2^522 mod r
-            Fr k522l;
-#pragma unroll
-            for (int t = 0; t < 8; t++) k522l.v[t] = c522l[t];
-            const uint32_t w1 = wd ? wd : 1u;
-            for (uint32_t i = 0; i < n; i++) {
-              const uint32_t pos = i * w1;
-              uint32_t m = 0;
-              if (pos < 256) {
-                const uint32_t lo = v.v[pos >> 5], hi = (pos >> 5) < 7 ? v.v[(pos >> 5) + 1] : 0u;
-                const uint64_t two = ((uint64_t)hi << 32) | lo;
-                m = (uint32_t)(two >> (pos & 31)) & ((1u << w1) - 1u);
-              }
-              Fr pm = Fr::zero();
-              pm.v[0] = m;
-              ST(d + i, fmul(pm, k522l));
-            }
+            for (uint32_t i = 0; i < n; i++) ST(d + i, f_small(limb_at(v, i * wd, wd)));
           }
           __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), as after CLS_BITS
-        }
-        if constexpr (EMUL) {
-          // CLS_EMUL: header (class, na + nb, n rows, aux), quad 0 = (OP_EMUL, first slot, 0, aux),
-          // aux = nout | na << 8 | first modulus constant << 12; the rows that follow hold the limb
-          // slots of a, then of b.  a = sum a_i 2^(64 i) (a limb may exceed 64 bits), b likewise,
-          // p = the four 64-bit constants: nout - 4 limbs of floor(a b / p), then four of a b mod p,
-          // into consecutive wires.  Sub-lane 0 works, as in CLS_HIST.
-          if ((hdr.x & 0xffu) == CLS_EMUL && !(hdr.x & 0x100u)) {
+        } else if constexpr (EMUL) {
+          if (hcls == CLS_EMUL) {
+            // sub-lane 0 works: the limbs of a and b from the nq slots of the unit's rows, the
+            // product, its quotient and remainder by the modulus (emul.h)
             const uint4 q0 = prog[(size_t)r * (1 + S) + 1];
-            const uint32_t nq = __builtin_amdgcn_readfirstlane(hdr.y);
-            const uint32_t nrows = __builtin_amdgcn_readfirstlane(hdr.z);
-            const uint32_t aux = __builtin_amdgcn_readfirstlane(hdr.w);
-            const uint32_t nk = (aux & 0xffu) - 4, na = (aux >> 8) & 0xfu, c0 = aux >> 12;
+            const uint32_t nk = vemul_nout(aux) - 4, na = vemul_na(aux), c0 = vemul_const0(aux);
             if (sl == 0) {
               uint32_t A[12], B[12], T[24], Rm[9], P[8];
 #pragma unroll
@@ -458,7 +406,7 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
               const uint4* pr = prog + (size_t)(r + 1) * (1 + S) + 1;
               for (uint32_t t = 0; t < nq; t++) {
                 const uint4 p = pr[(size_t)(t / S) * (1 + S) + (t % S)];
-                if ((p.x & 0x1fu) != OP_HQ) continue;
+                if (vq_op(p.x) != OP_HQ) continue;
                 const Fr v = f_plain(LD(p.z));
                 if (t < na)
                   emul_acc_at(A, v.v, t);
@@ -473,27 +421,11 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
               }
               emul_mul(T, A, B);
               emul_divmod(T, Rm, P);
-              constexpr uint32_t c522[8] = {0x45b69bd4u, 0x38c2e14bu, 0x85883377u, 0x0ffedb18u,
-                                            0xabc6e54du, 0x7840f9f0u, 0x848b0f05u, 0x0a054a3eu};   // 2^522 mod r
-              Fr k522;
 #pragma unroll
-              for (int t = 0; t < 8; t++) k522.v[t] = c522[t];
+              for (int j = 0; j < 8; j++)
+                if ((uint32_t)j < nk) ST(q0.y + j, f_small(T[2 * j], T[2 * j + 1]));
 #pragma unroll
-              for (int j = 0; j < 8; j++) {
-                if ((uint32_t)j < nk) {
-                  Fr pm = Fr::zero();
-                  pm.v[0] = T[2 * j];
-                  pm.v[1] = T[2 * j + 1];
-                  ST(q0.y + j, fmul(pm, k522));
-                }
-              }
-#pragma unroll
-              for (int j = 0; j < 4; j++) {
-                Fr pm = Fr::zero();
-                pm.v[0] = Rm[2 * j];
-                pm.v[1] = Rm[2 * j + 1];
-                ST(q0.y + nk + j, fmul(pm, k522));
-              }
+              for (int j = 0; j < 4; j++) ST(q0.y + nk + j, f_small(Rm[2 * j], Rm[2 * j + 1]));
             }
             r += nrows;
             __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -541,23 +473,20 @@ static Fr k_to_std() {  // 2^251
   k.v[7] = 1u << 27;
   return k;
 }
-int rows_to_f_domain(zkmi_ctx* ctx, Fr* base, size_t rows, size_t Bp) {
+static int scale_rows(zkmi_ctx* ctx, Fr* base, size_t rows, size_t Bp, const Fr& k) {
   if (rows == 0) return ZKMI_OK;
   size_t g = (rows * Bp + 255) / 256;
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)g), dim3(256), 0, ctx->stream, base, rows,
-                     Bp, k_to_f());
+                     Bp, k);
   ZK_HIP(hipGetLastError());
   return ZKMI_OK;
 }
+int rows_to_f_domain(zkmi_ctx* ctx, Fr* base, size_t rows, size_t Bp) {
+  return scale_rows(ctx, base, rows, Bp, k_to_f());
+}
 int rows_to_std_domain(zkmi_ctx* ctx, Fr* base, size_t rows, size_t Bp) {
-  if (rows == 0) return ZKMI_OK;
-  size_t g = (rows * Bp + 255) / 256;
-  if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)g), dim3(256), 0, ctx->stream, base, rows,
-                     Bp, k_to_std());
-  ZK_HIP(hipGetLastError());
-  return ZKMI_OK;
+  return scale_rows(ctx, base, rows, Bp, k_to_std());
 }
 int array_to_f_domain(zkmi_ctx* ctx, Fr* a, size_t n) {
   if (n == 0) return ZKMI_OK;
@@ -586,33 +515,34 @@ int solve_bi(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr* b, Fr* c, i
   return solve_rows(ctx, cs, slots, a, b, c, status, Bp, 0, cs->n_rows);
 }
 
+// one wavefront per 64 / S proofs; the instance with the big-integer division arm only for programs
+// that hold OP_EMUL units
+template <int S>
+static void launch_solve(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr* b, Fr* c,
+                         int32_t* status, size_t Bp, uint32_t row_begin, uint32_t row_end) {
+  hipLaunchKernelGGL((cs->has_emul ? solve_vliw_kernel<S, true> : solve_vliw_kernel<S, false>),
+                     dim3((unsigned)(Bp * S / 64)), dim3(64), 0, ctx->stream,
+                     (const uint4*)cs->program, cs->consts, slots, a, b, c, status, Bp, cs->n_rows,
+                     row_begin, row_end);
+}
+
 int solve_rows(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr* b, Fr* c, int32_t* status,
                size_t Bp, uint32_t row_begin, uint32_t row_end) {
   if (row_begin >= row_end) return ZKMI_OK;
-  // one wavefront per 64 / S proofs
-  const uint32_t S = cs->lanes_per_proof;
-  const dim3 grid((unsigned)(Bp * S / 64)), block(64);
-  const uint4* prog = (const uint4*)cs->program;
-#define ZK_SOLVE(SS)                                                                          \
-  if (cs->has_emul)                                                                               \
-    hipLaunchKernelGGL((solve_vliw_kernel<SS, true>), grid, block, 0, ctx->stream, prog,          \
-                       cs->consts, slots, a, b, c, status, Bp, cs->n_rows, row_begin, row_end);   \
-  else                                                                                            \
-    hipLaunchKernelGGL((solve_vliw_kernel<SS, false>), grid, block, 0, ctx->stream, prog,         \
-                       cs->consts, slots, a, b, c, status, Bp, cs->n_rows, row_begin, row_end)
-  switch (S) {
-    case 1: ZK_SOLVE(1); break;
-    case 2: ZK_SOLVE(2); break;
-    case 4: ZK_SOLVE(4); break;
-    case 8: ZK_SOLVE(8); break;
-    case 16: ZK_SOLVE(16); break;
-    case 32: ZK_SOLVE(32); break;
-    case 64: ZK_SOLVE(64); break;
+  decltype(&launch_solve<1>) launch;
+  switch (cs->lanes_per_proof) {
+    case 1: launch = launch_solve<1>; break;
+    case 2: launch = launch_solve<2>; break;
+    case 4: launch = launch_solve<4>; break;
+    case 8: launch = launch_solve<8>; break;
+    case 16: launch = launch_solve<16>; break;
+    case 32: launch = launch_solve<32>; break;
+    case 64: launch = launch_solve<64>; break;
     default:
       ctx->err = "cs: lanes_per_proof must be a power of two, 1 .. 64";
       return ZKMI_ERR_ARG;
   }
-#undef ZK_SOLVE
+  launch(ctx, cs, slots, a, b, c, status, Bp, row_begin, row_end);
   ZK_HIP(hipGetLastError());
   return ZKMI_OK;
 }

@@ -8,6 +8,7 @@
 
 #include "../../include/zkmi.h"
 #include "ec.h"
+#include "vprog.h"   // the witness program format: opcodes, classes, loader checks
 
 namespace zk {
 
@@ -224,10 +225,6 @@ __device__ __forceinline__ void bi_st_nt(Fr* base, size_t row, size_t b, size_t 
   __builtin_nontemporal_store(hi, p + Bp);
 }
 #endif
-
-// witness-program opcodes (frontend/api.py)
-enum { OP_END = 0, OP_ADD, OP_SUB, OP_MUL, OP_MULC, OP_ADDC, OP_NEG, OP_INV, OP_BITS, OP_SETC,
-       OP_ABC, OP_COPY, OP_DIV, OP_BATCHINV, OP_PAIR, OP_MULABC, OP_XORABC, OP_XOR, OP_FMAC, OP_FMA };
 
 #define ZK_HIP(call)                                                         \
   do {                                                                       \

@@ -73,3 +73,37 @@ def compiled(name):
         from gnark_crypto_primitives_amd.frontend.scs import compile_scs
         return compile_scs(compiled("address"))
     raise KeyError(name)
+
+
+def malformed_unit_rows(cc):
+    """(what is wrong, program, lanes_per_proof) for the unit rows of a compiled ArithCircuit (OP_EMUL,
+    packed limb steps, OP_HIST): every slot / constant / count that the loader must refuse, one broken
+    word each -- shared by the loader's GPU test and the host test of csrc/vprog.h."""
+    from gnark_crypto_primitives_amd.frontend import schedule as sch
+    hdr = cc.vprogram[:, 0, 0]
+    emul = int(np.nonzero(hdr == sch.CLS_EMUL)[0][0])
+    limbs = int(np.nonzero(hdr == sch.CLS_LIMBS)[0][0])
+    hist = int(np.nonzero(hdr == sch.CLS_HIST)[0][0])
+    S = cc.lanes_per_proof
+
+    def broken(row, quad, word, value):
+        p = cc.vprogram.copy()
+        p[row, quad, word] = value
+        return p
+
+    aux = int(cc.vprogram[emul, 0, 3])
+    past_pool = cc.vprogram.copy()
+    past_pool[emul, 0, 3] = past_pool[emul, 1, 3] = (aux & 0xfff) | (len(cc.consts) - 3) << 12
+    return [
+        ("outputs run past the wires", broken(emul, 1, 1, cc.n_wires - 2), S),
+        ("header / quad disagree on aux", broken(emul, 0, 3, aux ^ 0x100), S),
+        ("operand slot out of range", broken(emul + 1, 1, 2, cc.v_n_slots), S),
+        ("operand count without its rows", broken(emul, 0, 1, 9), S),
+        ("source slot out of range", broken(limbs, 1, 2, cc.v_n_slots), S),
+        ("more than 16 limbs in a packed step", broken(limbs, 1, 3, 17 | 13 << 16), S),
+        ("limb width above 16", broken(limbs, 1, 3, 4 | 17 << 16), S),
+        ("counters run past the wires", broken(hist, 1, 1, cc.n_wires - 1), S),
+        ("query slot out of range", broken(hist + 1, 1, 2, cc.v_n_slots), S),
+        ("modulus constants past the pool", past_pool, S),
+        ("sub-lane count not a power of two", cc.vprogram.copy(), 12),
+    ]
