@@ -128,6 +128,71 @@ __global__ __launch_bounds__(256) void field_mul_bench_f29_kernel(Fq* io, int it
   pack_canonical<Fq29Params>(io[i].v, norm(add(x, y)));
 }
 
+// ---- parity hook for the 9 x 29-bit forms (zkmi_ff29_op) ------------------------------------------
+// One lane per element, one wavefront per block.  The form is applied to the raw limbs as they are
+// in memory: nothing is unpacked or normalised, so operands at the edges of a form's contract reach
+// it unchanged.  Ops 0..3 are the asm chains of ff29_asm.h, 4..7 the C++ forms of ff29.h compiled
+// for the device, 8 and 9 pack_canonical with and without wred (8 words out, the ninth zero).
+enum { FF29_MUL_ASM, FF29_SQR_ASM, FF29_MUL_ADD2_ASM, FF29_MUL_ASM_S, FF29_MUL, FF29_SQR,
+       FF29_MUL_ADD2, FF29_MUL_ILP, FF29_WRED_PACK, FF29_PACK, FF29_N_OPS };
+static constexpr int ff29_arity(int op) {
+  if (op == FF29_MUL_ADD2_ASM || op == FF29_MUL_ADD2) return 4;
+  if (op == FF29_SQR_ASM || op == FF29_SQR || op == FF29_WRED_PACK || op == FF29_PACK) return 1;
+  return 2;
+}
+template <class P>
+__device__ __forceinline__ F29<P> ld_raw29(const int32_t* p) {
+  F29<P> r;
+#pragma unroll
+  for (int l = 0; l < 9; l++) r.v[l] = p[l];
+  return r;
+}
+template <class P, int OP>
+__global__ __launch_bounds__(64) void ff29_op_kernel(const int32_t* __restrict__ in,
+                                                     int32_t* __restrict__ out, size_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int AR = ff29_arity(OP);
+  for (size_t w = blockIdx.x; w * 64 < n; w += gridDim.x) {
+    // mul_asm_s: the b operand of the wave's first element, at an address that depends on the block
+    // index alone, so that (as ntt.hip's ldc29 twiddles) it reaches the asm in SGPRs
+    F29<P> bs = F29<P>::zero();
+    if constexpr (OP == FF29_MUL_ASM_S) bs = ld_raw29<P>(in + w * 64 * (AR * 9) + 9);
+    const size_t i = w * 64 + threadIdx.x;
+    if (i >= n) continue;
+    const int32_t* e = in + i * (AR * 9);
+    const F29<P> a = ld_raw29<P>(e);
+    F29<P> r = F29<P>::zero();
+    if constexpr (OP == FF29_MUL_ASM) r = mul_asm(a, ld_raw29<P>(e + 9));
+    if constexpr (OP == FF29_SQR_ASM) r = sqr_asm(a);
+    if constexpr (OP == FF29_MUL_ADD2_ASM)
+      r = mul_add2_asm(a, ld_raw29<P>(e + 9), ld_raw29<P>(e + 18), ld_raw29<P>(e + 27));
+    if constexpr (OP == FF29_MUL_ASM_S) r = mul_asm_s(a, bs);
+    if constexpr (OP == FF29_MUL) r = mul(a, ld_raw29<P>(e + 9));
+    if constexpr (OP == FF29_SQR) r = sqr(a);
+    if constexpr (OP == FF29_MUL_ADD2)
+      r = mul_add2(a, ld_raw29<P>(e + 9), ld_raw29<P>(e + 18), ld_raw29<P>(e + 27));
+    if constexpr (OP == FF29_MUL_ILP) r = mul_ilp(a, ld_raw29<P>(e + 9));
+    if constexpr (OP == FF29_WRED_PACK || OP == FF29_PACK) {
+      uint32_t img[8];
+      pack_canonical<P>(img, OP == FF29_WRED_PACK ? wred(a) : a);
+#pragma unroll
+      for (int l = 0; l < 8; l++) r.v[l] = (int32_t)img[l];
+      r.v[8] = 0;
+    }
+#pragma unroll
+    for (int l = 0; l < 9; l++) out[i * 9 + l] = r.v[l];
+  }
+#endif
+}
+typedef void (*ff29_kernel_t)(const int32_t*, int32_t*, size_t);
+template <class P, int OP = 0>
+static ff29_kernel_t ff29_kernel(int op) {
+  if constexpr (OP < FF29_N_OPS)
+    return op == OP ? ff29_op_kernel<P, OP> : ff29_kernel<P, OP + 1>(op);
+  else
+    return nullptr;
+}
+
 // ---- proof assembly ---------------------------------------------------------------------------------
 // Ar = sumA + alpha + r*delta ; Bs1 = sumB1 + beta + s*delta ; Bs = sumB2 + beta2 + s*delta2 ;
 // Krs = sumK + sumZ - rs*delta + s*Ar + r*Bs1.
@@ -430,6 +495,28 @@ int zkmi_field_mul(zkmi_ctx* ctx, int which, const void* a, const void* b, void*
                        (const Fq*)sa.dev, (const Fq*)sb.dev, (Fq*)sr.dev, n);
   ZK_HIP(hipGetLastError());
   if ((rc = sr.finish())) return rc;
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  return ZKMI_OK;
+}
+
+int zkmi_ff29_op(zkmi_ctx* ctx, int field, int op, const int32_t* in, int32_t* out, size_t n) {
+  ZK_HIP(hipSetDevice(ctx->device));
+  const ff29_kernel_t k = field == 0   ? ff29_kernel<Fr29Params>(op)
+                          : field == 1 ? ff29_kernel<Fq29Params>(op)
+                                       : nullptr;
+  if (!k) {
+    ctx->err = "ff29_op: field must be 0 (fr) or 1 (fq), op in [0, 9]";
+    return ZKMI_ERR_ARG;
+  }
+  if (n == 0) return ZKMI_OK;
+  Staged si(ctx), so(ctx);
+  int rc;
+  if ((rc = si.in(in, n * ff29_arity(op) * 36)) || (rc = so.out(out, n * 36))) return rc;
+  const size_t waves = (n + 63) / 64;
+  hipLaunchKernelGGL(k, dim3((unsigned)std::min(waves, (size_t)65536)), dim3(64), 0, ctx->stream,
+                     (const int32_t*)si.dev, (int32_t*)so.dev, n);
+  ZK_HIP(hipGetLastError());
+  if ((rc = so.finish())) return rc;
   ZK_HIP(hipStreamSynchronize(ctx->stream));
   return ZKMI_OK;
 }

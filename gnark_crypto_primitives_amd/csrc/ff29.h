@@ -362,9 +362,20 @@ ZK_HD F29<P> mul_add2(const F29<P>& a, const F29<P>& b, const F29<P>& c, const F
 
 // weak reduction of a value with |v| < 2^7 p (limbs below 2^31 in magnitude): subtract the
 // multiple of p estimated from the top limb; result normalised with |v| < 0.6 p.
+// The carry propagation is norm()'s, except that a limb next to +-2^31 plus an incoming carry must
+// not leave 32 bits: the carry meets the limb's low 29 bits only, and the limb's own high part
+// (a >> 29, in [-4, 3]) joins the outgoing carry afterwards.
 template <class P>
 ZK_HD F29<P> wred(const F29<P>& a) {
-  const F29<P> v = norm(a);
+  F29<P> v;
+  int32_t cy = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int32_t t = (a.v[i] & F29<P>::MASK) + cy;
+    v.v[i] = t & F29<P>::MASK;
+    cy = (t >> 29) + (a.v[i] >> 29);
+  }
+  v.v[8] = a.v[8] + cy;
   const float ptop = (float)P::p(8) + 0.5f;
   const int32_t q = (int32_t)__builtin_rintf((float)v.v[8] / ptop);
   F29<P> r;

@@ -63,6 +63,7 @@ SYMBOLS = [
     ("zkmi_sync", _I, [_P]),
     ("zkmi_stream", _P, [_P]),
     ("zkmi_field_mul", _I, [_P, _I, _P, _P, _P, _SZ]),
+    ("zkmi_ff29_op", _I, [_P, _I, _I, _P, _P, _SZ]),
     ("zkmi_field_mul_bench", _I, [_P, _I, _SZ, _I, C.POINTER(C.c_double)]),
     ("zkmi_ntt_batch", _I, [_P, _P, _I, _SZ, _I, _I]),
     ("zkmi_h_batch", _I, [_P, _P, _P, _P, _P, _I, _SZ]),
@@ -176,6 +177,14 @@ class Context:
         out = np.empty_like(a) if out is None else out
         self._check(self.lib.zkmi_field_mul(self.h, which, _ptr(a), _ptr(b), _ptr(out), n),
                     "zkmi_field_mul")
+        return out
+
+    def ff29_op(self, field, op, operands, out=None):
+        """operands: int32 [n][arity][9] raw limbs -> int32 [n][9] (zkmi_ff29_op)"""
+        n = operands.shape[0]
+        out = np.empty((n, 9), dtype=np.int32) if out is None else out
+        self._check(self.lib.zkmi_ff29_op(self.h, field, op, _ptr(operands), _ptr(out), n),
+                    "zkmi_ff29_op")
         return out
 
     def field_mul_bench(self, which=1, n_threads=1 << 20, iters=256) -> float:

@@ -52,6 +52,19 @@ void* zkmi_stream(zkmi_ctx* ctx);
 /* -- field / group primitives (parity tests; a Go shim that keeps gnark's own solver) ------- */
 /* r[i] = a[i] * b[i] in fr (which = 0) or fp (which = 1).   stands in for fr.Element.Mul / fp.Element.Mul */
 int zkmi_field_mul(zkmi_ctx* ctx, int which, const void* a, const void* b, void* r, size_t n);
+/* Parity hook for the 9 x 29-bit field forms every hot kernel multiplies with (csrc/ff29.h and the
+ * generated csrc/ff29_asm.h; tests/test_gpu_primitives.py::test_ff29_asm_products).  One lane per
+ * element applies form `op` of `field` (0 = fr, 1 = fq) to raw signed limbs, which are neither
+ * unpacked nor normalised on the way in:
+ *   in  [n][arity][9] int32, out [n][9] int32; n = 0 is a no-op, n need not be a multiple of 64;
+ *   op 0 mul_asm (a, b)   1 sqr_asm (a)   2 mul_add2_asm (a, b, c, d: a b + c d)   3 mul_asm_s (a, b)
+ *      4 mul   5 sqr   6 mul_add2   7 mul_ilp      -- the C++ forms, compiled for the device
+ *      8 pack_canonical(wred(a))   9 pack_canonical(a)   -- 8 packed words in out[0..7], out[8] = 0
+ *   mul_asm_s takes a wave-uniform b: element i uses the b operand of element 64 * (i / 64), loaded
+ *   through a wave-uniform index so that it reaches the asm in SGPRs, as the NTT's twiddles do; the
+ *   b operands of the other elements are read by nobody.
+ * An unknown field or op returns ZKMI_ERR_ARG. */
+int zkmi_ff29_op(zkmi_ctx* ctx, int field, int op, const int32_t* in, int32_t* out, size_t n);
 /* Throughput microbenchmark: every lane runs `iters` dependent Montgomery products; returns
  * products per second in *rate (integer-ALU roofline measurement).  which: 0 = fr,
  * 1 = fp (8 x 32-bit limbs, ff.h), 2 = fp in the 9 x 29-bit form the G1 MSM uses (ff29.h). */

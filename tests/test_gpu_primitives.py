@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from tests import ff29_ref
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -144,3 +145,88 @@ def test_empty_batches(zk_ctx):
     zk_ctx.h_batch(e, e, e, e.copy(), 4, 0)
     zk_ctx.fixed_base_mul(1, H.g1_gen_mont(), np.zeros((0, 4), dtype=np.uint64), 0,
                           np.zeros((0, 8), dtype=np.uint64))
+
+
+# ---- the 9 x 29-bit field forms at the edges of their contracts (tests/ff29_ref.py) ---------------
+@pytest.mark.parametrize("op", range(len(ff29_ref.OPS)), ids=ff29_ref.OPS)
+@pytest.mark.parametrize("field", [0, 1], ids=["fr", "fq"])
+def test_ff29_asm_products(zk_ctx, field, op):
+    """zkmi_ff29_op: the asm chains of ff29_asm.h, the C++ forms of ff29.h as the device compiler
+    builds them, and wred / pack_canonical, bit for bit against the big-integer reference on raw
+    limbs: limbs next to 2^29 (2^30 for mul's lazy operand, 2^31 for wred), values next to 8p,
+    negative and all-non-positive operands, products = 0 mod p (exactly 0 or p), negative results,
+    wred's float quotient at its rounding boundaries.  Class lengths include 1 and ragged waves."""
+    for name, operands, want in ff29_ref.vectors(field, op):
+        got = zk_ctx.ff29_op(field, op, operands)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert not len(bad), (f"{ff29_ref.FIELDS[field]} {ff29_ref.OPS[op]} class {name}: "
+                              f"{len(bad)} of {len(want)} differ, first at element {bad[0]}: "
+                              f"operands {operands[bad[0]].tolist()} got {got[bad[0]].tolist()} "
+                              f"want {want[bad[0]].tolist()}")
+
+
+def test_ff29_op_arguments(zk_ctx):
+    """n = 0 touches nothing; an unknown field or op is ZKMI_ERR_ARG (-1), not a launch."""
+    from gnark_crypto_primitives_amd import lib
+    out = np.full((1, 9), 7, dtype=np.int32)
+    for op in range(10):
+        zk_ctx.ff29_op(1, op, np.zeros((0, 4, 9), dtype=np.int32), out)
+    assert (out == 7).all()
+    one = np.zeros((1, 4, 9), dtype=np.int32)
+    for field, op in ((2, 0), (-1, 0), (0, 10), (1, -1), (0, 1 << 20)):
+        with pytest.raises(lib.ZkmiError, match=r"\(-1\)"):
+            zk_ctx.ff29_op(field, op, one, out)
+    assert (out == 7).all()
+
+
+_LAZY_EDGE_CACHE = {}
+
+
+def _lazy_edge_batch(log_n):
+    """Proofs that drive the 29-bit transforms' lazy operands to their bounds: all r-1, all 1, one
+    r-1 at row 0 / n-1 / n/2, alternating 0 / r-1, w^(k i) for k in {0, 1, n/2, n-1} (the whole sum
+    lands in ONE output row), and two random proofs.  Montgomery images, [12][n][4] uint64."""
+    if log_n not in _LAZY_EDGE_CACHE:
+        n = 1 << log_n
+        w = pow(5, (H.R - 1) >> log_n, H.R)
+        rows = [[H.R - 1] * n, [1] * n]
+        for at in (0, n - 1, n // 2):
+            rows.append([H.R - 1 if i == at else 0 for i in range(n)])
+        rows.append([(H.R - 1) * (i & 1) for i in range(n)])
+        for k in (0, 1, n // 2, n - 1):
+            wk, x, row = pow(w, k, H.R), 1, []
+            for _ in range(n):
+                row.append(x)
+                x = x * wk % H.R
+            rows.append(row)
+        r = H.rng(900 + log_n)
+        rows += [H.rand_fr(r, n)[0] for _ in range(2)]
+        data = np.stack([H.to_mont_array(row) for row in rows])
+        data.setflags(write=False)
+        _LAZY_EDGE_CACHE[log_n] = data
+    return _LAZY_EDGE_CACHE[log_n]
+
+
+@pytest.mark.parametrize("log_n", [8, 9, 10, 11, 12])
+@pytest.mark.parametrize("inverse,coset", [(0, 0), (1, 0), (0, 1), (1, 1)])
+def test_ntt_lazy_edges(zk_ctx, cref, log_n, inverse, coset):
+    """test_ntt's parity on structured vectors: ntt_mid29<1,2,3>, remainder 0 and a middle LDS
+    pass, with butterflies whose sums and differences sit at the ends of their value ranges."""
+    data = _lazy_edge_batch(log_n)
+    want = np.stack([cref.ntt(row, log_n, inverse, coset) for row in data])
+    got = data.copy()
+    zk_ctx.ntt_batch(got, log_n, len(got), inverse, coset)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("log_n", [8, 9, 10, 11, 12])
+def test_h_lazy_edges(zk_ctx, cref, log_n):
+    """The same vectors as a, b, c of the quotient (each proof meets two others): the fused pass
+    and the sub_after epilogue on operands at their bounds."""
+    a = _lazy_edge_batch(log_n)
+    b, c = np.roll(a, 1, axis=0), np.roll(a, 5, axis=0)
+    want = np.stack([cref.compute_h(a[i], b[i], c[i], log_n)
+                     for i in range(len(a))])
+    out = np.zeros_like(a)
+    zk_ctx.h_batch(a.copy(), b.copy(), c.copy(), out, log_n, len(a))
+    assert np.array_equal(out, want)
