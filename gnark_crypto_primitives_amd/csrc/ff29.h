@@ -17,7 +17,8 @@
 //              normalised values (|limb| < 2^29), or one operand with |limb| < 2^30;
 //              |a * b| < 64 p^2.  Result normalised, value in (-p/2, 3p/2).
 //   add/sub/neg: limb-wise, no normalisation.  norm(): carry propagation.
-// The memory image (tables, kernel outputs) stays 8 x u32: canonical value in [0, p).
+// The memory image (tables, kernel outputs) stays 8 x u32: canonical value in [0, p).  Between
+// the passes of one transform chain the NTT keeps a signed image instead (pack_lazy below).
 #pragma once
 #include "ff.h"
 
@@ -302,6 +303,34 @@ ZK_HD void pack_canonical(uint32_t w[8], const F29<P>& a) {
     }
   }
   if (wi < 8) w[wi] = (uint32_t)acc;
+}
+
+// The lazy memory image: a normalised value with |v| < 2^255 (wred's output, |v| < 0.6 p) as a
+// signed 256-bit two's-complement integer, 8 x u32.  No conditional +p / -p and no carry chain:
+// the limbs are shifted into place and limb 8 (bit 232, the sign carrier, |v[8]| < 2^23) sign-
+// extends through word 7.  For a value in [0, 2^255) it is the plain integer, so unpack_lazy also
+// reads every canonical image.  Only code that unpacks with unpack_lazy may read such a buffer
+// (the transform passes of ntt.hip among themselves); what leaves them is pack_canonical's.
+template <class P>
+ZK_HD void pack_lazy(uint32_t w[8], const F29<P>& a) {
+  uint64_t acc = 0;
+  int have = 0, wi = 0;
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    acc |= (uint64_t)(uint32_t)a.v[i] << have;   // limb 8: the u32 cast keeps the sign bits
+    have += 29;
+    if (have >= 32) {
+      w[wi++] = (uint32_t)acc;
+      acc >>= 32;
+      have -= 32;
+    }
+  }
+}
+template <class P>
+ZK_HD F29<P> unpack_lazy(const uint32_t w[8]) {
+  F29<P> r = unpack29<P>(w);
+  r.v[8] = (int32_t)w[7] >> 8;  // arithmetic: the sign of the 256-bit integer
+  return r;
 }
 
 // standard Montgomery element (R = 2^256, canonical) -> F29 domain (R' = 2^261)

@@ -37,17 +37,16 @@ struct NttPlan {
   Fr* tw_inv = nullptr;     // w^-i, i < n/2: `tw`, inverse
   Fr* coset_fwd = nullptr;  // g^i, i < n: `pre` of a forward coset transform on the ff.h passes
   Fr* coset_inv = nullptr;  // g^-i / n, i < n: `post` of inverse coset transform, ff.h and 29-bit
+  Fr* coset_inv_den = nullptr;  // g^-i / (n (g^n - 1)): `post` of the quotient's final transform
   // and factors passed by value:
   Fr n_inv;                 // 1/n: `post_uniform` of an inverse transform, ff.h and 29-bit
   Fr den;                   // 1/(g^n - 1): `den` of pointwise_h_kernel
   Fr ninv_den;              // den / n: `post_uniform` of the quotient's transform of c
   // The F domain (x * 2^261, canonical, packed 8 x u32: ff29.h).  Device tables:
-  Fr* tw29_fwd = nullptr;      // w^i: `tw` of the 29-bit passes, `tw_fwd` of the fused pass
-  Fr* tw29_inv = nullptr;      // w^-i: `tw` of the 29-bit passes, `tw_inv` of the fused pass
+  Fr* tw29_fwd = nullptr;      // w^i: `tw` of the 29-bit passes, forward half of a fused pass
+  Fr* tw29_inv = nullptr;      // w^-i: `tw` of the 29-bit passes, inverse half of a fused pass
   Fr* coset29_fwd = nullptr;   // g^i: `pre` of a forward coset transform on the 29-bit passes
-  Fr* coset29n_fwd = nullptr;  // g^i / n: `scale` of the fused pass (inverse -> coset forward)
-  // and a factor passed by value:
-  Fr den29;                 // 1/(g^n - 1): `den29` of pointwise_h29_kernel
+  Fr* coset29n_fwd = nullptr;  // g^i / n: `factor` of the fused pass inverse -> coset forward
 };
 
 }  // namespace zk
