@@ -716,6 +716,8 @@ void zkmi_msm_bases_free(zkmi_ctx* ctx, zkmi_msm_bases* b) {
   delete b;
 }
 
+uint32_t zkmi_comb_min_groups_per_chunk(void) { return COMB_MIN_GROUPS_PER_CHUNK; }
+
 int zkmi_msm_batch(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const void* scalars, size_t batch,
                    void* out) {
   ZK_HIP(hipSetDevice(ctx->device));

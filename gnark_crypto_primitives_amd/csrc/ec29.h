@@ -201,4 +201,173 @@ ZK_HD G1XYZZ to_std(const G1Acc29& a) {
   return G1XYZZ{to_std(a.x), to_std(a.y), to_std(a.zz), to_std(a.zzz)};
 }
 
+// ---- sums of accumulators (the chunk reduction of the MSM) ----------------------------------------
+// The accumulate kernels leave their chunk partials in the 2^261 domain: a Part29 holds x, y, zz and
+// zzz as lazy memory images (ff29.h pack_lazy: a normalised value with |v| < 2^255 as a signed
+// 256-bit integer), so neither side of the hand-over pays a domain change.  The word containers are
+// Fq / Fq2 only to have the size and alignment of an XYZZ<F>; a Part29 is never a field element of
+// ff.h.  Infinity: every word of zz zero (a finite point has zz != 0 mod p, and the image of a
+// non-zero residue is never the integer 0).
+// What is packed: x weakly reduced (|v| < 0.6p; canonical table values, 0 <= v < p, pass wred
+// unchanged in range), y in (-p, 3p/2), zz and zzz products in (-p/2, 3p/2); all normalised.
+template <class F>
+struct Part29 {
+  F x, y, zz, zzz;
+};
+static_assert(sizeof(Part29<Fq>) == sizeof(G1XYZZ) && sizeof(Part29<Fq2>) == sizeof(G2XYZZ),
+              "a packed partial takes the place of an XYZZ");
+
+ZK_HD void pack_lazy2(Fq2& w, const Fq2_29& a) {
+  pack_lazy<Fq29Params>(w.c0.v, a.c0);
+  pack_lazy<Fq29Params>(w.c1.v, a.c1);
+}
+ZK_HD Fq2_29 unpack_lazy2(const Fq2& w) {
+  return {unpack_lazy<Fq29Params>(w.c0.v), unpack_lazy<Fq29Params>(w.c1.v)};
+}
+
+// G1: madd29 leaves |x| < 5p, which the image cannot hold: x goes through wred (a no-op in value
+// for padd29's results, which are weakly reduced already)
+ZK_HD Part29<Fq> pack_part(const G1Acc29& a) {
+  Part29<Fq> r;
+  if (a.inf) {
+    r.x = r.y = r.zz = r.zzz = Fq::zero();
+    return r;
+  }
+  pack_lazy<Fq29Params>(r.x.v, wred(a.x));
+  pack_lazy<Fq29Params>(r.y.v, a.y);
+  pack_lazy<Fq29Params>(r.zz.v, a.zz);
+  pack_lazy<Fq29Params>(r.zzz.v, a.zzz);
+  return r;
+}
+ZK_HD G1Acc29 unpack_part(const Part29<Fq>& w) {
+  G1Acc29 a;
+  a.inf = w.zz.is_zero();
+  a.x = unpack_lazy<Fq29Params>(w.x.v);
+  a.y = unpack_lazy<Fq29Params>(w.y.v);
+  a.zz = unpack_lazy<Fq29Params>(w.zz.v);
+  a.zzz = unpack_lazy<Fq29Params>(w.zzz.v);
+  return a;
+}
+// G2: x and y are weakly reduced (or a table entry's components) after every step
+ZK_HD Part29<Fq2> pack_part(const G2Acc29& a) {
+  Part29<Fq2> r;
+  if (a.inf) {
+    r.x = r.y = r.zz = r.zzz = Fq2::zero();
+    return r;
+  }
+  pack_lazy2(r.x, a.x);
+  pack_lazy2(r.y, a.y);
+  pack_lazy2(r.zz, a.zz);
+  pack_lazy2(r.zzz, a.zzz);
+  return r;
+}
+ZK_HD G2Acc29 unpack_part(const Part29<Fq2>& w) {
+  G2Acc29 a;
+  a.inf = w.zz.is_zero();
+  a.x = unpack_lazy2(w.x);
+  a.y = unpack_lazy2(w.y);
+  a.zz = unpack_lazy2(w.zz);
+  a.zzz = unpack_lazy2(w.zzz);
+  return a;
+}
+
+ZK_HD Fq2_29 from_std(const Fq2& x) {
+  return {from_std<Fq29Params>(x.c0), from_std<Fq29Params>(x.c1)};
+}
+// standard XYZZ -> accumulator (the results of from_std are products: within every bound above)
+ZK_HD G1Acc29 from_std(const G1XYZZ& p) {
+  if (p.is_inf()) return G1Acc29::infinity();
+  G1Acc29 a;
+  a.x = from_std<Fq29Params>(p.x);
+  a.y = from_std<Fq29Params>(p.y);
+  a.zz = from_std<Fq29Params>(p.zz);
+  a.zzz = from_std<Fq29Params>(p.zzz);
+  a.inf = false;
+  return a;
+}
+ZK_HD G2Acc29 from_std(const G2XYZZ& p) {
+  if (p.is_inf()) return G2Acc29::infinity();
+  G2Acc29 a;
+  a.x = from_std(p.x);
+  a.y = from_std(p.y);
+  a.zz = from_std(p.zz);
+  a.zzz = from_std(p.zzz);
+  a.inf = false;
+  return a;
+}
+
+// acc += b, both accumulators (add-2008-s).  Operands as unpack_part or an earlier padd29 leaves
+// them: x, y normalised with |x| < p, |y| < 3p/2; zz, zzz products, (-p/2, 3p/2).  The result keeps
+// these bounds (x weakly reduced, y a product), so sums chain without limit: chunk sums, then
+// group sums, then the common addend.
+// Equal x (pp = 0: the same point twice, or a point and its negative) is left to ec.h.
+ZK_HD void padd29(G1Acc29& acc, const G1Acc29& b) {
+  if (b.inf) return;
+  if (acc.inf) {
+    acc = b;
+    return;
+  }
+  const Fq29 u1 = mmul(acc.x, b.zz);    // |a b| < 1.5 p^2; every product below is in (-p/2, 3p/2)
+  const Fq29 u2 = mmul(b.x, acc.zz);
+  const Fq29 s1 = mmul(acc.y, b.zzz);   // < 2.25 p^2
+  const Fq29 s2 = mmul(b.y, acc.zzz);
+  const Fq29 p = sub(u2, u1);           // |limbs| < 2^29, |value| < 2p
+  const Fq29 r = sub(s2, s1);           // the same
+  const Fq29 pp = msqr(p);              // < 4 p^2
+  if (is_zero_mulout(pp)) {
+    G1XYZZ s = to_std(acc);
+    padd(s, to_std(b));
+    acc = from_std(s);
+    return;
+  }
+  const Fq29 rr = msqr(r);
+  const Fq29 ppp = mmul(p, pp);         // < 3 p^2
+  const Fq29 q = mmul(u1, pp);          // < 2.25 p^2
+  // rr - ppp - 2q in (-5p, 3p), limbs in (-3 * 2^29, 2^29): wred's range; |x3| < 0.6p
+  const Fq29 x3 = wred(sub(sub(rr, ppp), add(q, q)));
+  // one reduction for both products (madd29): |q - x3| < 2.1p, limbs a difference of normalised
+  // values; |r (q - x3)| + |s1 ppp| < 4.2 p^2 + 2.25 p^2
+  const Fq29 y3 = mmul_add2(r, sub(q, x3), neg(s1), ppp);
+  acc.zz = mmul(mmul(acc.zz, b.zz), pp);
+  acc.zzz = mmul(mmul(acc.zzz, b.zzz), ppp);
+  acc.x = x3;
+  acc.y = y3;
+}
+
+// G2: components of x, y normalised with |v| < p; of zz, zzz products.  An Fq2 product takes the
+// sum of two component products, each < 64 p^2 / 2.  p and r are normalised before they are
+// squared: msqr forms c0 + c1 and c0 - c1, and only one of the two may exceed 2^29 per limb.
+ZK_HD void padd29(G2Acc29& acc, const G2Acc29& b) {
+  if (b.inf) return;
+  if (acc.inf) {
+    acc = b;
+    return;
+  }
+  const Fq2_29 u1 = mmul(acc.x, b.zz);    // 2 * 1.5 p^2; components of a product in (-p/2, 3p/2)
+  const Fq2_29 u2 = mmul(b.x, acc.zz);
+  const Fq2_29 s1 = mmul(acc.y, b.zzz);
+  const Fq2_29 s2 = mmul(b.y, acc.zzz);
+  const Fq2_29 p = norm(sub(u2, u1));     // |component| < 2p
+  const Fq2_29 r = norm(sub(s2, s1));
+  const Fq2_29 pp = msqr(p);              // (c0 + c1)(c0 - c1), 2 c0 c1: < 16 p^2
+  if (is_zero_mulout(pp)) {
+    G2XYZZ s = to_std(acc);
+    padd(s, to_std(b));
+    acc = from_std(s);
+    return;
+  }
+  const Fq2_29 rr = msqr(r);
+  const Fq2_29 ppp = mmul(p, pp);         // 2 * 3 p^2
+  const Fq2_29 q = mmul(u1, pp);          // 2 * 2.25 p^2
+  // components of rr - ppp - 2q in (-5p, 3p), limbs in (-3 * 2^29, 2^29); |x3| < 0.6p
+  const Fq2_29 x3 = wred(sub(sub(rr, ppp), add(q, q)));
+  // |q - x3| < 2.1p per component: 2 * 4.2 p^2 and 2 * 2.25 p^2; the difference of the two products
+  // has |component| < 2p, |y3| < 0.6p
+  const Fq2_29 y3 = wred(sub(mmul(r, sub(q, x3)), mmul(s1, ppp)));
+  acc.zz = mmul(mmul(acc.zz, b.zz), pp);
+  acc.zzz = mmul(mmul(acc.zzz, b.zzz), ppp);
+  acc.x = x3;
+  acc.y = y3;
+}
+
 }  // namespace zk

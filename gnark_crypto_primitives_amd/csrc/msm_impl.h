@@ -137,8 +137,8 @@ template <> struct CombAcc<Fq> {
                                              int32_t (*)[256], uint32_t) {
     Acc29<Fq>::add(acc, e, negd);
   }
-  static __device__ __forceinline__ G1XYZZ result(const type& acc, int32_t (*)[256], uint32_t) {
-    return to_std(acc);
+  static __device__ __forceinline__ Part29<Fq> result(const type& acc, int32_t (*)[256], uint32_t) {
+    return pack_part(acc);
   }
 };
 struct G2AccL {
@@ -214,9 +214,16 @@ template <> struct CombAcc<Fq2> {
     acc.x = x3;
     acc.y = y3;
   }
-  static __device__ __forceinline__ G2XYZZ result(const type& acc, int32_t (*z)[256], uint32_t t) {
-    if (acc.inf) return G2XYZZ::inf();
-    return G2XYZZ{to_std(acc.x), to_std(acc.y), to_std(lds_ld2(z, 0, t)), to_std(lds_ld2(z, 18, t))};
+  static __device__ __forceinline__ Part29<Fq2> result(const type& acc, int32_t (*z)[256], uint32_t t) {
+    G2Acc29 a = G2Acc29::infinity();
+    if (!acc.inf) {
+      a.x = acc.x;
+      a.y = acc.y;
+      a.zz = lds_ld2(z, 0, t);
+      a.zzz = lds_ld2(z, 18, t);
+      a.inf = false;
+    }
+    return pack_part(a);
   }
 };
 
@@ -227,7 +234,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
                                                       const Fr* __restrict__ scalars,
                                                       const uint32_t* __restrict__ row_idx,
                                                       size_t Bp, uint32_t n, uint32_t per_chunk,
-                                                      WinPlan plan, XYZZ<F>* __restrict__ partial,
+                                                      WinPlan plan, Part29<F>* __restrict__ partial,
                                                       Fr kmul, const uint8_t* __restrict__ inf) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t chunk = blockIdx.y;
@@ -262,7 +269,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void m
       }
     }
   }
-  partial[(size_t)chunk * Bp + b] = to_std(acc);
+  partial[(size_t)chunk * Bp + b] = pack_part(acc);
 }
 
 // ---- shared-table path: one table per base, one accumulator per (window, chunk) -------------------
@@ -323,7 +330,7 @@ template <class F>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void
 msm_accumulate_shared(const Affine<F>* __restrict__ table, const int16_t* __restrict__ digits,
                       size_t Bp, uint32_t n, uint32_t per_chunk, uint32_t per_base,
-                      XYZZ<F>* __restrict__ partial) {
+                      Part29<F>* __restrict__ partial) {
   // (an XCD-aware deal of the chunks -- all blocks of a chunk on one L2 -- measured no better)
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t chunk = blockIdx.z, j = blockIdx.y;
@@ -341,7 +348,7 @@ msm_accumulate_shared(const Affine<F>* __restrict__ table, const int16_t* __rest
       Acc29<F>::add(acc, e, negd);
     }
   }
-  partial[((size_t)j * gridDim.z + chunk) * Bp + b] = to_std(acc);
+  partial[((size_t)j * gridDim.z + chunk) * Bp + b] = pack_part(acc);
 }
 
 // out[b] = sum_j 2^(pos_j) * wsum[j][b]; blockIdx.y selects one of up to four independent sums
@@ -641,19 +648,31 @@ __global__ __launch_bounds__(256) void comb_digits_kernel(const Fr* __restrict__
   }
 }
 
+// Chunks in use when nv groups vary: a chunk costs the reduction about 1.25 additions of two
+// accumulators plus the packing, ~2.2 mixed additions, so a chunk has to be worth
+// COMB_MIN_GROUPS_PER_CHUNK of them.  The accumulate kernel and the reduction both derive the
+// count from counts[0] on the device; the grid (grid_chunks) is sized from all groups on the host.
+__host__ __device__ inline uint32_t comb_eff_chunks(uint32_t nv, uint32_t grid_chunks) {
+  const uint32_t want = (nv + COMB_MIN_GROUPS_PER_CHUNK - 1) / COMB_MIN_GROUPS_PER_CHUNK;
+  return want < 1 ? 1 : want > grid_chunks ? grid_chunks : want;
+}
+
 // grid: x over proofs, y over the windows (254, or 255 for signed tables), z over chunks of the
-// varying groups: the grid is sized from n_groups, each block takes its share of counts[0]
-// (an empty chunk leaves the identity)
+// varying groups: the grid is sized from n_groups, the first comb_eff_chunks blocks of z share
+// counts[0] groups (an empty chunk leaves the identity: chunk 0 when nothing varies), the others
+// leave at once and write nothing
 template <class F, bool CHECK_INF, bool SIGNED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void
 msm_accumulate_comb(const Affine<F>* __restrict__ table, const uint32_t* __restrict__ digits,
                     size_t Bp, uint32_t n_groups, const uint32_t* __restrict__ vlist,
                     const uint32_t* __restrict__ counts, uint32_t per_group,
-                    XYZZ<F>* __restrict__ partial) {
-  const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+                    Part29<F>* __restrict__ partial) {
   const uint32_t chunk = blockIdx.z, j = blockIdx.y;
   const uint32_t nv = counts[0];
-  const uint32_t per_chunk = (nv + gridDim.z - 1) / gridDim.z;
+  const uint32_t eff = comb_eff_chunks(nv, gridDim.z);
+  if (chunk >= eff) return;
+  const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t per_chunk = (nv + eff - 1) / eff;
   const uint32_t p0 = chunk * per_chunk;
   uint32_t p1 = p0 + per_chunk;
   if (p1 > nv) p1 = nv;
@@ -690,7 +709,8 @@ static __device__ __forceinline__ T shfl_xor_words(const T& x, int mask) {
 }
 
 // usum[j] = sum over the uniform groups g = ulist[c] of T[g][d0[j][g]]: the part of window sum j
-// that every proof of the batch shares, added once per lane by the last msm_reduce pass.  One
+// that every proof of the batch shares, added once per lane by the last msm_reduce pass (stored
+// packed, as the partials are).  One
 // block of 256 lanes per window; each lane sums a strided share of the groups, then a butterfly
 // over the wave and the four wave sums through LDS.  Same entries as msm_accumulate_comb would
 // gather, so the window sums are unchanged (a group sum does not depend on the order).
@@ -701,7 +721,7 @@ __global__ __launch_bounds__(256) void comb_common_sums(const Affine<F>* __restr
                                                         const uint32_t* __restrict__ ulist,
                                                         const uint32_t* __restrict__ counts,
                                                         uint32_t per_group,
-                                                        XYZZ<F>* __restrict__ usum) {
+                                                        Part29<F>* __restrict__ usum) {
   const uint32_t j = blockIdx.x, t = threadIdx.x;
   const uint32_t nu = counts[1];
   const uint32_t* dj = d0 + (size_t)j * n_groups;
@@ -734,7 +754,7 @@ __global__ __launch_bounds__(256) void comb_common_sums(const Affine<F>* __restr
       for (int i = 0; i < NW; i++) ow[i] = wave_sum[q][i];
       padd(s, o);
     }
-    usum[j] = s;
+    usum[j] = pack_part(from_std(s));
   }
 }
 
@@ -801,27 +821,36 @@ static void launch_comb_horner(hipStream_t stream, const HornerArgsRW<F>& ha, in
 
 // sums groups of `group` consecutive chunk partials: out[g][b] = sum_{k < group} in[g*group + k][b]
 // (blockIdx.z selects an independent set: partial += z * in_zstride, out += z * out_zstride);
-// addend (may be null): addend[z] is added to every sum of set z (comb_common_sums)
-template <class F>
-__global__ __launch_bounds__(64) void msm_reduce(const XYZZ<F>* __restrict__ partial, size_t Bp,
-                                                 uint32_t chunks, uint32_t group,
-                                                 XYZZ<F>* __restrict__ out, size_t in_zstride,
-                                                 size_t out_zstride,
-                                                 const XYZZ<F>* __restrict__ addend) {
+// addend (may be null): addend[z] is added to every sum of set z (comb_common_sums).
+// Partials, group sums and the addend are packed accumulators (ec29.h); the LAST pass writes the
+// final sums as XYZZ<F> for what follows.
+// counts (comb tables; null: all `chunks` inputs are summed): only the first
+// comb_eff_chunks(counts[0], grid_chunks) chunk partials were written by this batch's accumulate
+// launch, the other slots hold an earlier batch's.  This pass sums the first ceil(eff / div)
+// inputs: div = 1 over the chunk partials, div = the first level's group size over its group
+// sums; a group that starts beyond them is skipped and its output never read.
+template <class F, bool LAST>
+__global__ __launch_bounds__(64) void msm_reduce(
+    const Part29<F>* __restrict__ partial, size_t Bp, uint32_t chunks, uint32_t group,
+    typename std::conditional<LAST, XYZZ<F>, Part29<F>>::type* __restrict__ out, size_t in_zstride,
+    size_t out_zstride, const Part29<F>* __restrict__ addend, const uint32_t* __restrict__ counts,
+    uint32_t grid_chunks, uint32_t div) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= Bp) return;
+  if (counts) chunks = (comb_eff_chunks(counts[0], grid_chunks) + div - 1) / div;
   partial += (size_t)blockIdx.z * in_zstride;
   out += (size_t)blockIdx.z * out_zstride;
   const uint32_t k0 = blockIdx.y * group;
+  if (k0 >= chunks) return;
   uint32_t k1 = k0 + group;
   if (k1 > chunks) k1 = chunks;
-  XYZZ<F> acc = partial[(size_t)k0 * Bp + b];
-  for (uint32_t k = k0 + 1; k < k1; k++) {
-    XYZZ<F> p = partial[(size_t)k * Bp + b];
-    padd(acc, p);
-  }
-  if (addend) padd(acc, addend[blockIdx.z]);
-  out[(size_t)blockIdx.y * Bp + b] = acc;
+  typename Acc29<F>::type acc = unpack_part(partial[(size_t)k0 * Bp + b]);
+  for (uint32_t k = k0 + 1; k < k1; k++) padd29(acc, unpack_part(partial[(size_t)k * Bp + b]));
+  if (addend) padd29(acc, unpack_part(addend[blockIdx.z]));
+  if constexpr (LAST)
+    out[(size_t)blockIdx.y * Bp + b] = to_std(acc);
+  else
+    out[(size_t)blockIdx.y * Bp + b] = pack_part(acc);
 }
 
 template <class F>
@@ -946,37 +975,47 @@ static inline ChunkSplit split_chunks(size_t items, size_t want) {
 
 // out[w][b] = sum of the chunk partials partial[w][chunk][b] for each of W independent sets, through
 // the group sums mid[w][group][b] when there is more than one group.  addend (may be null):
-// addend[w] joins every sum of set w in the last pass.
+// addend[w] joins every sum of set w in the last pass.  counts (may be null): see msm_reduce.
 template <class F>
 static void reduce_partials(hipStream_t stream, const XYZZ<F>* partial, XYZZ<F>* mid, XYZZ<F>* out,
-                            size_t Bp, const ChunkSplit& cs, int W, const XYZZ<F>* addend) {
-  const XYZZ<F>* in = partial;
-  uint32_t count = (uint32_t)cs.chunks;
+                            size_t Bp, const ChunkSplit& cs, int W, const XYZZ<F>* addend,
+                            const uint32_t* counts) {
+  const Part29<F>* in = (const Part29<F>*)partial;
+  uint32_t count = (uint32_t)cs.chunks, div = 1;
   if (cs.ngroups > 1) {
-    hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), cs.ngroups, (unsigned)W), dim3(64),
-                       0, stream, in, Bp, count, cs.group, mid, (size_t)count * Bp,
-                       (size_t)cs.ngroups * Bp, (const XYZZ<F>*)nullptr);
-    in = mid;
+    hipLaunchKernelGGL((msm_reduce<F, false>), dim3((unsigned)(Bp / 64), cs.ngroups, (unsigned)W),
+                       dim3(64), 0, stream, in, Bp, count, cs.group, (Part29<F>*)mid,
+                       (size_t)count * Bp, (size_t)cs.ngroups * Bp, (const Part29<F>*)nullptr, counts,
+                       (uint32_t)cs.chunks, div);
+    in = (const Part29<F>*)mid;
     count = cs.ngroups;
+    div = cs.group;
   }
-  hipLaunchKernelGGL((msm_reduce<F>), dim3((unsigned)(Bp / 64), 1, (unsigned)W), dim3(64), 0, stream,
-                     in, Bp, count, count, out, (size_t)count * Bp, Bp, addend);
+  hipLaunchKernelGGL((msm_reduce<F, true>), dim3((unsigned)(Bp / 64), 1, (unsigned)W), dim3(64), 0,
+                     stream, in, Bp, count, count, out, (size_t)count * Bp, Bp,
+                     (const Part29<F>*)addend, counts, (uint32_t)cs.chunks, div);
 }
 
 // msm_part[pb] of the comb and shared-table routines: the chunk partials [W][chunks][Bp], the group
 // sums [W][ngroups][Bp], the window sums [W][Bp] (unused when the caller takes them), and for comb
-// tables the W common sums of the uniform groups.
+// tables the W common sums of the uniform groups and the two counts of comb_split_kernel.  Only
+// wsum holds XYZZ<F> values: the other sums are packed accumulators of the same size (Part29<F>,
+// ec29.h).  The counts are here and not beside the group lists because the reduction reads them,
+// possibly on the finish stream while the main stream already splits the next MSM's groups.
 template <class F>
 struct PartView {
   XYZZ<F> *partial, *mid, *wsum, *usum;
+  uint32_t* counts;
   static size_t bytes(const ChunkSplit& cs, int W, size_t Bp, bool common_sums) {
-    return ((cs.chunks + cs.ngroups + 1) * W * Bp + (common_sums ? W : 0)) * sizeof(XYZZ<F>);
+    return ((cs.chunks + cs.ngroups + 1) * W * Bp + (common_sums ? W : 0)) * sizeof(XYZZ<F>) +
+           (common_sums ? 2 * sizeof(uint32_t) : 0);
   }
   PartView(void* base, const ChunkSplit& cs, int W, size_t Bp) {
     partial = (XYZZ<F>*)base;
     mid = partial + cs.chunks * W * Bp;
     wsum = mid + (size_t)cs.ngroups * W * Bp;
     usum = wsum + (size_t)W * Bp;
+    counts = (uint32_t*)(usum + W);
   }
 };
 
@@ -1025,8 +1064,8 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
   // writes the other partial buffer
   const bool defer = wsum_out && finish_stream && finish_stream != ctx->stream;
   const int pb = defer ? (int)(ctx->part_next++ & 1u) : 0;
-  // (the common sums are read by the last reduction, which may run on finish_stream: they are
-  // under part_ev as well)
+  // (the common sums and the counts are read by the reduction, which may run on finish_stream:
+  // they are under part_ev as well)
   int rc = ensure_scratch(ctx, ctx->msm_part[pb], PartView<F>::bytes(cs, W, Bp, true), &part);
   if (rc) return rc;
   if ((rc = wait_partials_free(ctx, pb))) return rc;
@@ -1034,9 +1073,9 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
   // buffers -- correct, no gain: the pass is ALU work like the accumulate kernel it would hide
   // under, which slowed down by exactly the pass's 7 ms.)
   // digits [W][G][Bp] (the first |vlist| rows of every window are used), then lane 0's digits of
-  // the uniform groups [W][G] and the split of the groups: gvar, vlist, ulist, vpos [G], counts
+  // the uniform groups [W][G] and the split of the groups: gvar, vlist, ulist, vpos [G]
   if ((rc = ensure_scratch(ctx, ctx->msm_digits,
-                           ((size_t)W * G * Bp + (size_t)(W + 4) * G + 2) * sizeof(uint32_t),
+                           ((size_t)W * G * Bp + (size_t)(W + 4) * G) * sizeof(uint32_t),
                            &digits)))
     return rc;
   if ((rc = ensure_scratch(ctx, ctx->msm_sint, n * Bp * sizeof(Fr), &sint))) return rc;
@@ -1045,8 +1084,8 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
   uint32_t* vlist = gvar + G;
   uint32_t* ulist = vlist + G;
   uint32_t* vpos = ulist + G;
-  uint32_t* counts = vpos + G;
   const PartView<F> pv(part, cs, W, Bp);
+  uint32_t* counts = pv.counts;
   XYZZ<F>* wsum = wsum_out ? wsum_out : pv.wsum;
   const unsigned bx = (Bp % 256 == 0) ? 256 : 64;
   const dim3 sgrid((unsigned)(Bp / bx), (unsigned)(n < 16384 ? n : 16384));
@@ -1073,10 +1112,11 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
          : (sg ? msm_accumulate_comb<F, false, true> : msm_accumulate_comb<F, false, false>);
   hipLaunchKernelGGL(sums, dim3((unsigned)W), dim3(256), 0, ctx->stream,
                      (const Affine<F>*)bases->table, (const uint32_t*)d0, (uint32_t)G,
-                     (const uint32_t*)ulist, (const uint32_t*)counts, per_group, pv.usum);
+                     (const uint32_t*)ulist, (const uint32_t*)counts, per_group,
+                     (Part29<F>*)pv.usum);
   hipLaunchKernelGGL(accumulate, grid, dim3(bx), 0, ctx->stream, (const Affine<F>*)bases->table,
                      (const uint32_t*)digits, Bp, (uint32_t)G, (const uint32_t*)vlist,
-                     (const uint32_t*)counts, per_group, pv.partial);
+                     (const uint32_t*)counts, per_group, (Part29<F>*)pv.partial);
   acc_timer_end(ctx, timed);
   hipStream_t rq = ctx->stream;
   if (defer) {
@@ -1084,7 +1124,7 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
     ZK_HIP(hipStreamWaitEvent(finish_stream, ctx->acc_ev[pb], 0));
     rq = finish_stream;
   }
-  reduce_partials<F>(rq, pv.partial, pv.mid, wsum, Bp, cs, W, pv.usum);
+  reduce_partials<F>(rq, pv.partial, pv.mid, wsum, Bp, cs, W, pv.usum, counts);
   if (defer) {
     ZK_HIP(hipEventRecord(ctx->part_ev[pb], finish_stream));
     ctx->part_ev_valid[pb] = true;
@@ -1138,9 +1178,9 @@ int run_shared(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
   hipLaunchKernelGGL((msm_accumulate_shared<F>),
                      dim3((unsigned)(Bp / bx), (unsigned)W, (unsigned)cs.chunks), dim3(bx), 0,
                      ctx->stream, (const Affine<F>*)bases->table, (const int16_t*)digits, Bp,
-                     (uint32_t)n, cs.per_chunk, plan.per_base, pv.partial);
+                     (uint32_t)n, cs.per_chunk, plan.per_base, (Part29<F>*)pv.partial);
   acc_timer_end(ctx, timed);
-  reduce_partials<F>(ctx->stream, pv.partial, pv.mid, wsum, Bp, cs, W, nullptr);
+  reduce_partials<F>(ctx->stream, pv.partial, pv.mid, wsum, Bp, cs, W, nullptr, nullptr);
   if (!wsum_out) {
     HornerArgs<F> ha{};
     ha.wsum[0] = wsum;
@@ -1184,9 +1224,11 @@ int run_windows(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
   const hipEvent_t timed = (bases->side || n == 1) ? nullptr : acc_timer_begin(ctx, bases);
   hipLaunchKernelGGL((n == 1 ? msm_accumulate<F, true> : msm_accumulate<F, false>), grid, dim3(bx), 0,
                      ctx->stream, (const Affine<F>*)bases->table, scalars, row_idx, Bp, (uint32_t)n,
-                     cs.per_chunk, bases->plan, partial, kmul, (const uint8_t*)bases->inf);
+                     cs.per_chunk, bases->plan, (Part29<F>*)partial, kmul,
+                     (const uint8_t*)bases->inf);
   acc_timer_end(ctx, timed);
-  reduce_partials<F>(ctx->stream, partial, partial + cs.chunks * Bp, out, Bp, cs, 1, nullptr);
+  reduce_partials<F>(ctx->stream, partial, partial + cs.chunks * Bp, out, Bp, cs, 1, nullptr,
+                     nullptr);
   ZK_HIP(hipGetLastError());
   return ZKMI_OK;
 }

@@ -274,6 +274,8 @@ int compute_h_bi(zkmi_ctx* ctx, const NttPlan* plan, Fr* a, Fr* b, Fr* c, Fr* t0
 
 // msm.hip (the templates behind these are in msm_impl.h)
 constexpr int COMB_W = 254;   // one-bit windows of a comb plan: scalars are below 2^254
+// fewest varying groups that are worth a chunk of their own (msm_impl.h comb_eff_chunks)
+constexpr uint32_t COMB_MIN_GROUPS_PER_CHUNK = 32;
 // window plans: per-window tables (of W windows; of c-bit windows), one shared table of c-bit
 // windows, comb tables over groups of k bases
 WinPlan plan_with_windows(int W);

@@ -70,6 +70,7 @@ SYMBOLS = [
     ("zkmi_msm_bases_load", _I, [_P, _I, _P, _SZ, _I, C.POINTER(_P)]),
     ("zkmi_msm_bases_free", None, [_P, _P]),
     ("zkmi_msm_batch", _I, [_P, _P, _P, _SZ, _P]),
+    ("zkmi_comb_min_groups_per_chunk", C.c_uint32, []),
     ("zkmi_fixed_base_mul", _I, [_P, _I, _P, _P, _SZ, _P]),
     ("zkmi_pk_load", _I, [_P, C.POINTER(PkDesc), C.POINTER(_P)]),
     ("zkmi_pk_free", None, [_P, _P]),
@@ -216,6 +217,9 @@ class Context:
         self._check(self.lib.zkmi_msm_batch(self.h, bases_h, _ptr(scalars), batch, _ptr(out)),
                     "zkmi_msm_batch")
         return out
+
+    def comb_min_groups_per_chunk(self):
+        return int(self.lib.zkmi_comb_min_groups_per_chunk())
 
     def fixed_base_mul(self, group, base, scalars, n, out):
         self._check(self.lib.zkmi_fixed_base_mul(self.h, group, _ptr(base), _ptr(scalars), n,

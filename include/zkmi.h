@@ -105,6 +105,9 @@ void zkmi_msm_bases_free(zkmi_ctx* ctx, zkmi_msm_bases* b);
  *   scalars: batch x n fr elements (Montgomery), proof-major; out: batch affine points. */
 int zkmi_msm_batch(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const void* scalars, size_t batch,
                    void* out);
+/* Comb tables: fewest groups with batch-varying scalars that are worth a chunk (a row of
+ * accumulate blocks and a partial sum of its own) in one MSM launch. */
+uint32_t zkmi_comb_min_groups_per_chunk(void);
 /* out[i] = scalars[i] * base.   stands in for curve.BatchScalarMultiplicationG1/G2 used by
  * groth16.Setup (gnark backend/groth16/bn254/setup.go). */
 int zkmi_fixed_base_mul(zkmi_ctx* ctx, int group, const void* base, const void* scalars, size_t n,
