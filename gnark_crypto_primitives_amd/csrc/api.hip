@@ -46,54 +46,6 @@ int require_idle(zkmi_ctx* ctx) {
   return ZKMI_ERR_ARG;
 }
 
-// RAII staging of a caller buffer (host or device) as device memory
-struct Staged {
-  zkmi_ctx* ctx;
-  void* dev = nullptr;
-  void* host = nullptr;  // non-null when a copy back is pending
-  size_t bytes = 0;
-  bool owned = false;
-  Staged(zkmi_ctx* c) : ctx(c) {}
-  int in(const void* p, size_t n) {
-    bytes = n;
-    if (n == 0) return ZKMI_OK;
-    if (pointer_kind(p) == PTR_DEVICE) {
-      dev = const_cast<void*>(p);
-      return ZKMI_OK;
-    }
-    ZK_HIP(hipMalloc(&dev, n));
-    owned = true;
-    ZK_HIP(hipMemcpyAsync(dev, p, n, hipMemcpyHostToDevice, ctx->stream));
-    return ZKMI_OK;
-  }
-  int out(void* p, size_t n) {
-    bytes = n;
-    if (n == 0) return ZKMI_OK;
-    if (pointer_kind(p) == PTR_DEVICE) {
-      dev = p;
-      return ZKMI_OK;
-    }
-    ZK_HIP(hipMalloc(&dev, n));
-    owned = true;
-    host = p;
-    return ZKMI_OK;
-  }
-  int finish() {
-    if (host && dev) {
-      ZK_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
-      ZK_HIP(hipStreamSynchronize(ctx->stream));
-      host = nullptr;
-    }
-    return ZKMI_OK;
-  }
-  ~Staged() {
-    if (owned && dev) {
-      hipStreamSynchronize(ctx->stream);
-      hipFree(dev);
-    }
-  }
-};
-
 // ---- elementwise field kernels --------------------------------------------------------------------
 template <class P>
 __global__ __launch_bounds__(256) void field_mul_kernel(const Fp<P>* a, const Fp<P>* b, Fp<P>* r,
@@ -323,9 +275,7 @@ static SetBytes prove_set_bytes(size_t value_rows, size_t n, size_t n_staged, si
   return {value_rows * Bp * 32, n * Bp * 32, Bp * (96 + 4) + batch * (n_staged * 32 + 64)};
 }
 
-// a caller array as device memory: used in place, or (host memory) copied into `stage` on
-// ctx->stream
-static int device_view(zkmi_ctx* ctx, const void* src, size_t bytes, void* stage, const void** out) {
+int device_view(zkmi_ctx* ctx, const void* src, size_t bytes, void* stage, const void** out) {
   *out = src;
   if (pointer_kind(src) == PTR_DEVICE) return ZKMI_OK;
   ZK_HIP(hipMemcpyAsync(stage, src, bytes, hipMemcpyHostToDevice, ctx->stream));

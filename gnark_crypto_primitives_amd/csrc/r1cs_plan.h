@@ -1,0 +1,295 @@
+// The solve plan of a gnark-shaped R1CS: the one definition of what zkmi_r1cs_solver_load builds
+// from the loaded matrices and a zkmi_r1cs_solver_desc, and what r1cs_solve_kernel (r1cs_solve.hip)
+// runs.  Host-compilable: tests/native/r1cs_plan_check.cpp builds plans and interprets them without
+// a GPU (tests/test_native_r1cs_plan.py).
+//
+// gnark's solver (constraint/bn254 solver.go [UPSTREAM-RECALL]) walks cs.Instructions once per
+// witness and finds, at run time, the one wire of each constraint that is not solved yet.  Which
+// wire that is depends on the system alone, not on the witness, so the builder does that walk once
+// with a solved-wire bitmap (ONE, the public and the secret inputs to begin with) and leaves the
+// kernel a list of records with the unknowns resolved.  No scheduling: the plan is the instruction
+// list in gnark's order.
+//
+// Record = two quads of 32-bit words, one per instruction:
+//   quad 0  (kind, target, coef, coef_inv)
+//     kind      RK_ASSERT    every wire known: check a b = c
+//               RK_SOLVE_O   the unknown x has coefficient k in O: x = (a b - c) / k
+//               RK_SOLVE_L   ... in L: x = (c / b - a) / k, b = 0 is unsatisfied   (RK_SOLVE_R alike)
+//               RK_INVZERO   hint: target = 1 / a, 0 for a = 0       (a = the hint's input expression)
+//               RK_NBITS     hint: bit i of the canonical value of a into wire outs[target + i]
+//     target    the wire solved (RK_NBITS: the first entry of the hint's output wires in `outs`)
+//     coef      RK_SOLVE_*: coefficient word of the unknown (as in the terms below)
+//     coef_inv  RK_SOLVE_*: index of 1 / k, appended to the coefficient table (inverted here, once)
+//   quad 1  (first term, product rows, unit rows, k)
+//     the instruction's KNOWN terms are terms[first .. first + S (product rows + unit rows)), and
+//     the next instruction's follow them without a gap:
+//     first the terms that need a product, padded to whole rows of S, then those with coefficient
+//     +1 / -1, padded likewise -- a row is one term per sub-lane, so the S sub-lanes of a proof never
+//     diverge inside a row.  k = constraint row the a, b, c of the instruction go to (RK_NBITS: the
+//     number of output wires).
+// Term = (wire | tag << 30, coefficient index | unit << 30): tag RT_L / RT_R / RT_O names the
+//   expression the term belongs to (hints: RT_L), RT_PAD a padding term (wire 0, adds nothing);
+//   unit 1 / 2 = the coefficient is +1 / -1, as zkmi_r1cs_load marks it.
+// The term array ends with R1CS_TERM_SLACK rows of padding terms and the records with one RK_ASSERT
+// record without terms: the kernel fetches three rows and one record ahead of what it runs.
+//
+// Every count the kernel loops over and every index it uses as an address comes out of
+// r1cs_plan_build, which has checked it: that is what bounds the kernel's accesses and its run time.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/zkmi.h"
+#include "ff.h"
+
+namespace zk {
+
+enum { RK_ASSERT = 0, RK_SOLVE_O, RK_SOLVE_L, RK_SOLVE_R, RK_INVZERO, RK_NBITS };
+enum { RT_L = 0, RT_R = 1, RT_O = 2, RT_PAD = 3 };
+constexpr uint32_t R1CS_IDX_MASK = 0x3fffffffu;   // low 30 bits of a term word
+constexpr uint32_t R1CS_TERM_SLACK = 3;           // rows of padding terms behind the last instruction
+
+struct R1csTerm {
+  uint32_t wire, coef;   // the loaded form: coef = coefficient index | unit << 30
+};
+struct R1csRecord {
+  uint32_t kind, target, coef, coef_inv;
+  uint32_t first, mul_rows, unit_rows, k;
+};
+
+// The loaded system (zkmi_r1cs, read back to the host) and the caller's solver description.
+struct R1csPlanIn {
+  uint32_t n_wires = 0, n_constraints = 0, n_coeffs = 0;
+  const Fr* coeffs = nullptr;             // 2^261 images (gnark's image times 2^5)
+  const uint32_t* ptr[3] = {};            // L, R, O: n_constraints + 1 offsets
+  const R1csTerm* terms[3] = {};
+  const zkmi_r1cs_solver_desc* desc = nullptr;   // host arrays
+};
+struct R1csPlan {
+  uint32_t S = 0, n_instr = 0;
+  std::vector<R1csRecord> records;   // n_instr + 1
+  std::vector<R1csTerm> terms;       // plan terms: (wire | tag << 30, coef)
+  std::vector<Fr> coeffs;            // the system's table, then the inverses (2^261 images)
+  std::vector<uint32_t> outs;        // output wires of the RK_NBITS hints
+  uint64_t n_terms = 0;              // known terms, without padding
+  uint32_t longest = 0;              // most known terms in one instruction
+  uint32_t n_inversions = 0;         // RK_SOLVE_L + RK_SOLVE_R + RK_INVZERO
+};
+
+// S for lanes_per_proof = 0: the power of two in 1 .. 16 nearest to the mean number of known terms
+// per instruction (the smaller one when two are equally near)
+inline uint32_t r1cs_auto_lanes(uint64_t n_terms, uint32_t n_instr) {
+  const double mean = n_instr ? (double)n_terms / n_instr : 1.0;
+  uint32_t best = 1;
+  for (uint32_t s = 2; s <= 16; s *= 2) {
+    const double d = mean > s ? mean - s : s - mean, db = mean > best ? mean - best : best - mean;
+    if (d < db) best = s;
+  }
+  return best;
+}
+
+inline const char* r1cs_hint_name(uint32_t kind) {
+  static const char* names[8] = {"kind 0", "InvZero", "NBits", "limbs (kind 3)",
+                                 "lookup multiplicities (kind 4)", "commitment (kind 5)",
+                                 "byte operation (kind 6)", "emulated product (kind 7)"};
+  return kind < 8 ? names[kind] : "of an unknown kind";
+}
+
+// Returns the empty string and the plan, or what is wrong with the description.
+inline std::string r1cs_plan_build(const R1csPlanIn& in, R1csPlan* out) {
+  const zkmi_r1cs_solver_desc& d = *in.desc;
+  const std::string pre = "r1cs solver: ";
+  if (in.n_wires == 0 || in.n_wires > R1CS_IDX_MASK || in.n_coeffs == 0 || in.n_coeffs > R1CS_IDX_MASK)
+    return pre + "the system needs 1 .. 2^30 - 1 wires and coefficients";
+  uint32_t S = d.lanes_per_proof;
+  if (S > 64 || (S & (S - 1))) return pre + "lanes_per_proof must be 0 (auto) or a power of two, 1 .. 64";
+  if (d.n_public == 0 || (uint64_t)d.n_public + d.n_secret > in.n_wires)
+    return pre + "n_public (which counts the ONE wire) + n_secret must be in 1 .. n_wires";
+  if (d.n_instr == 0 || !d.instr) return pre + "no instructions";
+  if (d.n_hints && (!d.hint_kind || !d.hint_in_ptr || !d.hint_lc_ptr || !d.hint_out_ptr))
+    return pre + "hint table: null array";
+  // the hint table's offsets, before any of them is used as an index
+  uint32_t n_lc = 0, n_hterms = 0, n_houts = 0;
+  if (d.n_hints) {
+    bool ok = d.hint_in_ptr[0] == 0 && d.hint_out_ptr[0] == 0;
+    for (uint32_t h = 0; ok && h < d.n_hints; h++)
+      ok = d.hint_in_ptr[h] <= d.hint_in_ptr[h + 1] && d.hint_out_ptr[h] <= d.hint_out_ptr[h + 1];
+    if (ok) {
+      n_lc = d.hint_in_ptr[d.n_hints];
+      n_houts = d.hint_out_ptr[d.n_hints];
+      ok = d.hint_lc_ptr[0] == 0;
+      for (uint32_t i = 0; ok && i < n_lc; i++) ok = d.hint_lc_ptr[i] <= d.hint_lc_ptr[i + 1];
+      if (ok) n_hterms = d.hint_lc_ptr[n_lc];
+    }
+    if (!ok || (n_hterms && !d.hint_terms) || (n_houts && !d.hint_out))
+      return pre + "hint table: offsets are not monotone from 0, or a null array";
+  }
+  // the matrices (zkmi_r1cs_load has checked them too; a plan must not depend on that)
+  static const char* names[3] = {"L", "R", "O"};
+  for (uint32_t s = 0; s < 3; s++) {
+    bool ok = in.ptr[s] && in.ptr[s][0] == 0;
+    for (uint32_t k = 0; ok && k < in.n_constraints; k++) ok = in.ptr[s][k] <= in.ptr[s][k + 1];
+    const uint32_t nnz = ok ? in.ptr[s][in.n_constraints] : 0;
+    ok = ok && (nnz == 0 || in.terms[s]);
+    for (uint32_t t = 0; ok && t < nnz; t++)
+      ok = in.terms[s][t].wire < in.n_wires && (in.terms[s][t].coef & R1CS_IDX_MASK) < in.n_coeffs;
+    if (!ok)
+      return pre + "malformed matrix " + names[s] +
+             " (offsets not monotone from 0, or a term's coefficient / wire index out of range)";
+  }
+  // +1 / -1 among the lifted coefficients (hint terms arrive unmarked)
+  Fr one32 = Fr::one();
+  for (int t = 0; t < 5; t++) one32 = add(one32, one32);
+  const Fr minus32 = neg(one32);
+  auto unit_of = [&](uint32_t cid) {
+    return in.coeffs[cid] == one32 ? 1u : in.coeffs[cid] == minus32 ? 2u : 0u;
+  };
+
+  std::vector<uint8_t> solved(in.n_wires, 0), row_seen(in.n_constraints, 0);
+  for (uint32_t i = 0; i < d.n_public + d.n_secret; i++) solved[i] = 1;
+
+  // pass 1: resolve the unknowns in instruction order
+  struct Pending {
+    uint32_t kind, target, coef, k;
+    std::vector<R1csTerm> mul, unit;   // known terms, tagged
+  };
+  std::vector<Pending> pend(d.n_instr);
+  std::vector<uint32_t> outs;
+  uint64_t n_terms = 0;
+  uint32_t longest = 0;
+  for (uint32_t ii = 0; ii < d.n_instr; ii++) {
+    const uint32_t ik = d.instr[2 * ii], idx = d.instr[2 * ii + 1];
+    const std::string at = pre + "instruction " + std::to_string(ii);
+    Pending& p = pend[ii];
+    auto known = [&](uint32_t wire, uint32_t coef, uint32_t tag) {
+      (coef >> 30 ? p.unit : p.mul).push_back(R1csTerm{wire | tag << 30, coef});
+    };
+    if (ik == 1) {
+      if (idx >= d.n_hints) return at + ": hint index " + std::to_string(idx) + " out of range";
+      const uint32_t hk = d.hint_kind[idx];
+      const std::string hat = at + " (hint " + std::to_string(idx) + ")";
+      if (hk != ZKMI_HINT_INVZERO && hk != ZKMI_HINT_NBITS)
+        return hat + ": hints " + r1cs_hint_name(hk) + " are not supported on this entry";
+      const uint32_t in0 = d.hint_in_ptr[idx], in1 = d.hint_in_ptr[idx + 1];
+      const uint32_t o0 = d.hint_out_ptr[idx], o1 = d.hint_out_ptr[idx + 1];
+      if (in1 != in0 + 1 || o1 == o0 || (hk == ZKMI_HINT_INVZERO && o1 != o0 + 1))
+        return hat + ": " + r1cs_hint_name(hk) + " takes one input" +
+               (hk == ZKMI_HINT_INVZERO ? " and has one output" : " and has outputs");
+      for (uint32_t t = d.hint_lc_ptr[in0]; t < d.hint_lc_ptr[in0 + 1]; t++) {
+        const uint32_t cid = d.hint_terms[t].coeff, wire = d.hint_terms[t].wire;
+        if (cid >= in.n_coeffs || wire >= in.n_wires)
+          return hat + ": a term's coefficient or wire index is out of range";
+        if (!solved[wire]) return hat + ": reads wire " + std::to_string(wire) + ", which is not solved yet";
+        known(wire, cid | unit_of(cid) << 30, RT_L);
+      }
+      for (uint32_t o = o0; o < o1; o++) {
+        const uint32_t wire = d.hint_out[o];
+        if (wire >= in.n_wires) return hat + ": output wire " + std::to_string(wire) + " out of range";
+        if (solved[wire]) return hat + ": output wire " + std::to_string(wire) + " is already solved";
+        solved[wire] = 1;
+      }
+      if (hk == ZKMI_HINT_INVZERO) {
+        p.kind = RK_INVZERO;
+        p.target = d.hint_out[o0];
+        p.k = 0;
+      } else {
+        p.kind = RK_NBITS;
+        p.target = (uint32_t)outs.size();
+        p.k = o1 - o0;
+        outs.insert(outs.end(), d.hint_out + o0, d.hint_out + o1);
+      }
+      p.coef = 0;
+    } else if (ik == 0) {
+      if (idx >= in.n_constraints) return at + ": constraint index " + std::to_string(idx) + " out of range";
+      const std::string cat = at + " (constraint " + std::to_string(idx) + ")";
+      if (row_seen[idx]) return cat + ": the constraint occurs twice";
+      row_seen[idx] = 1;
+      int64_t unk = -1;
+      uint32_t unk_coef = 0, unk_tag = 0;
+      for (uint32_t s = 0; s < 3; s++)
+        for (uint32_t t = in.ptr[s][idx]; t < in.ptr[s][idx + 1]; t++) {
+          const R1csTerm tm = in.terms[s][t];
+          if (solved[tm.wire]) {
+            known(tm.wire, tm.coef, s);
+            continue;
+          }
+          if (unk >= 0 && (uint32_t)unk != tm.wire)
+            return cat + ": two unknown wires (" + std::to_string(unk) + ", " + std::to_string(tm.wire) + ")";
+          if (unk >= 0)
+            return cat + ": the unknown wire " + std::to_string(unk) +
+                   (unk_tag == s ? " occurs twice in one expression" : " occurs in more than one of L, R, O");
+          unk = tm.wire;
+          unk_coef = tm.coef;
+          unk_tag = s;
+        }
+      p.k = idx;
+      p.kind = unk < 0 ? RK_ASSERT : unk_tag == RT_O ? RK_SOLVE_O : unk_tag == RT_L ? RK_SOLVE_L : RK_SOLVE_R;
+      p.target = unk < 0 ? 0 : (uint32_t)unk;
+      p.coef = unk_coef;
+      if (unk >= 0) {
+        if (in.coeffs[unk_coef & R1CS_IDX_MASK].is_zero())
+          return cat + ": the unknown wire " + std::to_string(unk) + " has coefficient 0";
+        solved[unk] = 1;
+      }
+    } else {
+      return at + ": kind " + std::to_string(ik) + " is neither a constraint (0) nor a hint (1)";
+    }
+    const uint32_t n = (uint32_t)(p.mul.size() + p.unit.size());
+    n_terms += n;
+    if (n > longest) longest = n;
+  }
+  for (uint32_t k = 0; k < in.n_constraints; k++)
+    if (!row_seen[k]) return pre + "constraint " + std::to_string(k) + " occurs in no instruction";
+  for (uint32_t w = 0; w < in.n_wires; w++)
+    if (!solved[w]) return pre + "wire " + std::to_string(w) + " is still unsolved after the last instruction";
+
+  if (S == 0) S = r1cs_auto_lanes(n_terms, d.n_instr);
+  // pass 2: lay the records and the padded term rows out
+  R1csPlan& P = *out;
+  P = R1csPlan();
+  P.S = S;
+  P.n_instr = d.n_instr;
+  P.n_terms = n_terms;
+  P.longest = longest;
+  P.outs = std::move(outs);
+  P.coeffs.assign(in.coeffs, in.coeffs + in.n_coeffs);
+  P.records.reserve((size_t)d.n_instr + 1);
+  const R1csTerm pad{(uint32_t)RT_PAD << 30, 0};
+  // 1 / k from the 2^261 image k 2^5 (as a Montgomery value): inverse() gives (1 / k) 2^-5, ten
+  // doublings the image (1 / k) 2^5 again
+  auto inverse_261 = [](const Fr& x) {
+    Fr r = inverse(x);
+    for (int t = 0; t < 10; t++) r = add(r, r);
+    return r;
+  };
+  for (uint32_t ii = 0; ii < d.n_instr; ii++) {
+    Pending& p = pend[ii];
+    R1csRecord r{p.kind, p.target, p.coef, 0, 0, 0, 0, p.k};
+    if (p.kind == RK_SOLVE_O || p.kind == RK_SOLVE_L || p.kind == RK_SOLVE_R) {
+      r.coef_inv = (uint32_t)P.coeffs.size();
+      P.coeffs.push_back(inverse_261(in.coeffs[p.coef & R1CS_IDX_MASK]));
+    }
+    if (p.kind == RK_SOLVE_L || p.kind == RK_SOLVE_R || p.kind == RK_INVZERO) P.n_inversions++;
+    r.mul_rows = (uint32_t)((p.mul.size() + S - 1) / S);
+    r.unit_rows = (uint32_t)((p.unit.size() + S - 1) / S);
+    const uint64_t first = P.terms.size();
+    if (first + (uint64_t)(r.mul_rows + r.unit_rows + R1CS_TERM_SLACK) * S > 0xffffffffull)
+      return pre + "more than 2^32 plan terms";
+    r.first = (uint32_t)first;
+    P.terms.insert(P.terms.end(), p.mul.begin(), p.mul.end());
+    P.terms.resize(first + (size_t)r.mul_rows * S, pad);
+    P.terms.insert(P.terms.end(), p.unit.begin(), p.unit.end());
+    P.terms.resize(first + (size_t)(r.mul_rows + r.unit_rows) * S, pad);
+    P.records.push_back(r);
+    p.mul = std::vector<R1csTerm>();
+    p.unit = std::vector<R1csTerm>();
+  }
+  P.records.push_back(R1csRecord{RK_ASSERT, 0, 0, 0, (uint32_t)P.terms.size(), 0, 0, 0});
+  P.terms.resize(P.terms.size() + (size_t)R1CS_TERM_SLACK * S, pad);
+  if (P.coeffs.size() > R1CS_IDX_MASK) return pre + "coefficient table overflow";
+  return "";
+}
+
+}  // namespace zk

@@ -25,14 +25,6 @@
 
 using namespace zk;
 
-struct zkmi_r1cs {
-  uint32_t n_wires = 0, n_constraints = 0, n_coeffs = 0;
-  uint32_t* ptr[3] = {};   // device, n_constraints + 1 offsets each (L, R, O)
-  uint2* terms[3] = {};    // device, x = wire, y = coefficient index | kind << 30
-  size_t nnz[3] = {};
-  Fr* coeffs = nullptr;    // device, 2^261 images (gnark's Montgomery image times 2^5: fmul_261)
-};
-
 namespace zk {
 
 int pointer_kind(const void* p) {

@@ -197,6 +197,15 @@ struct zkmi_cs {
   bool has_emul = false;
 };
 
+// the R1CS matrices of zkmi_r1cs_load (witness.hip)
+struct zkmi_r1cs {
+  uint32_t n_wires = 0, n_constraints = 0, n_coeffs = 0;
+  uint32_t* ptr[3] = {};   // device, n_constraints + 1 offsets each (L, R, O)
+  uint2* terms[3] = {};    // device, x = wire, y = coefficient index | kind << 30
+  size_t nnz[3] = {};
+  zk::Fr* coeffs = nullptr;   // device, 2^261 images (gnark's Montgomery image times 2^5: fmul_261)
+};
+
 namespace zk {
 
 #if defined(__HIPCC__)
@@ -244,6 +253,57 @@ int require_idle(zkmi_ctx* ctx);
 enum { PTR_PAGEABLE = 0, PTR_PINNED = 1, PTR_DEVICE = 2 };
 int pointer_kind(const void* p);
 void witness_ring_free(zkmi_ctx* ctx);
+
+// RAII staging of a caller buffer (host or device) as device memory
+struct Staged {
+  zkmi_ctx* ctx;
+  void* dev = nullptr;
+  void* host = nullptr;  // non-null when a copy back is pending
+  size_t bytes = 0;
+  bool owned = false;
+  Staged(zkmi_ctx* c) : ctx(c) {}
+  int in(const void* p, size_t n) {
+    bytes = n;
+    if (n == 0) return ZKMI_OK;
+    if (pointer_kind(p) == PTR_DEVICE) {
+      dev = const_cast<void*>(p);
+      return ZKMI_OK;
+    }
+    ZK_HIP(hipMalloc(&dev, n));
+    owned = true;
+    ZK_HIP(hipMemcpyAsync(dev, p, n, hipMemcpyHostToDevice, ctx->stream));
+    return ZKMI_OK;
+  }
+  int out(void* p, size_t n) {
+    bytes = n;
+    if (n == 0) return ZKMI_OK;
+    if (pointer_kind(p) == PTR_DEVICE) {
+      dev = p;
+      return ZKMI_OK;
+    }
+    ZK_HIP(hipMalloc(&dev, n));
+    owned = true;
+    host = p;
+    return ZKMI_OK;
+  }
+  int finish() {
+    if (host && dev) {
+      ZK_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+      ZK_HIP(hipStreamSynchronize(ctx->stream));
+      host = nullptr;
+    }
+    return ZKMI_OK;
+  }
+  ~Staged() {
+    if (owned && dev) {
+      hipStreamSynchronize(ctx->stream);
+      hipFree(dev);
+    }
+  }
+};
+// a caller array as device memory: used in place, or (host memory) copied into `stage` on
+// ctx->stream
+int device_view(zkmi_ctx* ctx, const void* src, size_t bytes, void* stage, const void** out);
 
 // One Groth16 submit (zkmi_prove_submit, zkmi_prove_witness_submit) on set ctx->next_submit.
 // prove_set_begin sizes that set and the idle one (value file of `value_rows`, `n_staged` input

@@ -288,7 +288,54 @@ class Prover:
         self.r1cs_h = self.ctx.r1cs_load(rd)
         return self.r1cs_h
 
+    def load_r1cs_solver(self, lanes_per_proof=0):
+        """zkmi_r1cs_solver_load: the GPU solver of the gnark-shaped system, described the way a
+        gnark ccs describes it -- L, R, O, the instruction order and the hint table.  The frontend's
+        solve wires and its witness program are deliberately left out: the library finds every
+        constraint's unknown itself.  lanes_per_proof: 0 = auto, or a power of two, 1 .. 64; a
+        solver loaded with another value is replaced."""
+        if getattr(self, "r1cs_solver_h", None):
+            if lanes_per_proof == self._r1cs_solver_lanes:
+                return self.r1cs_solver_h
+            self.ctx.r1cs_solver_free(self.r1cs_solver_h)
+            self.r1cs_solver_h = None
+        cc = self.cc
+        kinds, in_ptr, lc_ptr, hcol, hcid, out_ptr, outs = cc.hint_arrays
+        arrs = [np.ascontiguousarray(x, dtype=np.uint32) for x in
+                (cc.instr, kinds, in_ptr, lc_ptr, np.stack([hcid, hcol], axis=1), out_ptr, outs)]
+        sd = _lib.R1csSolverDesc(cc.n_public, cc.n_secret, cc.instr.shape[0], len(kinds),
+                                 *[a.ctypes.data for a in arrs], lanes_per_proof)
+        self.r1cs_solver_h = self.ctx.r1cs_solver_load(self.load_r1cs(), sd)
+        self._r1cs_solver_lanes = lanes_per_proof
+        return self.r1cs_solver_h
+
+    def _r1cs_solver(self):
+        return getattr(self, "r1cs_solver_h", None) or self.load_r1cs_solver()
+
+    def solve_r1cs(self, inputs, want_wires=True, want_abc=False):
+        """Witness solve only, by the gnark-shaped solver (zkmi_r1cs_solve_batch); as ``solve``.
+        Uses the solver ``load_r1cs_solver`` loaded last, or loads one with the automatic lanes."""
+        batch = inputs.shape[0]
+        self._check_batch(inputs, (batch, self.n_inputs, 4), "inputs")
+        wires = np.zeros((batch, self.cc.n_wires, 4), np.uint64) if want_wires else None
+        abc = np.zeros((3, batch, self.cc.n_constraints, 4), np.uint64) if want_abc else None
+        status = self.ctx.r1cs_solve_batch(self._r1cs_solver(), np.ascontiguousarray(inputs),
+                                           batch, wires, abc)
+        return status, wires, abc
+
+    def submit_r1cs(self, inputs, rs):
+        """Stage 1 of a prove from inputs through the gnark-shaped solver
+        (zkmi_prove_r1cs_submit); ``collect`` returns the proofs."""
+        self._check_batch(inputs, (inputs.shape[0], self.n_inputs, 4), "inputs")
+        self._check_batch(rs, (inputs.shape[0], 2, 4), "rs")
+        self.ctx.prove_r1cs_submit(self.pk_h, self._r1cs_solver(), inputs, inputs.shape[0], rs)
+        self._inflight = getattr(self, "_inflight", [])
+        self._inflight.append((inputs, rs, inputs.shape[0]))     # keep buffers alive
+
     def close(self):
+        if getattr(self, "r1cs_solver_h", None):
+            self.ctx.r1cs_solver_free(self.r1cs_solver_h)
+            self.r1cs_solver_h = None
         if getattr(self, "r1cs_h", None):
             self.ctx.r1cs_free(self.r1cs_h)
             self.r1cs_h = None

@@ -54,6 +54,14 @@ class R1csDesc(C.Structure):
                 ("o_terms", C.c_void_p)]
 
 
+class R1csSolverDesc(C.Structure):
+    _fields_ = [("n_public", C.c_uint32), ("n_secret", C.c_uint32), ("n_instr", C.c_uint32),
+                ("n_hints", C.c_uint32), ("instr", C.c_void_p), ("hint_kind", C.c_void_p),
+                ("hint_in_ptr", C.c_void_p), ("hint_lc_ptr", C.c_void_p), ("hint_terms", C.c_void_p),
+                ("hint_out_ptr", C.c_void_p), ("hint_out", C.c_void_p),
+                ("lanes_per_proof", C.c_uint32)]
+
+
 # every symbol include/zkmi.h declares: (name, restype, argtypes)
 _P, _SZ, _I = C.c_void_p, C.c_size_t, C.c_int
 SYMBOLS = [
@@ -89,6 +97,11 @@ SYMBOLS = [
     ("zkmi_r1cs_load", _I, [_P, C.POINTER(R1csDesc), C.POINTER(_P)]),
     ("zkmi_r1cs_free", None, [_P, _P]),
     ("zkmi_prove_witness_submit", _I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _P]),
+    ("zkmi_r1cs_solver_load", _I, [_P, _P, C.POINTER(R1csSolverDesc), C.POINTER(_P)]),
+    ("zkmi_r1cs_solver_free", None, [_P, _P]),
+    ("zkmi_r1cs_solver_info", _I, [_P, C.POINTER(C.c_uint64)]),
+    ("zkmi_r1cs_solve_batch", _I, [_P, _P, _P, _SZ, _P, _P, _P]),
+    ("zkmi_prove_r1cs_submit", _I, [_P, _P, _P, _P, _SZ, _P]),
     ("zkmi_last_timings", _I, [_P, C.POINTER(C.c_double)]),
     ("zkmi_plonk_pk_load", _I, [_P, _P, C.POINTER(_P)]),
     ("zkmi_plonk_pk_free", None, [_P, _P]),
@@ -293,6 +306,34 @@ class Context:
 
     def r1cs_free(self, h):
         self.lib.zkmi_r1cs_free(self.h, h)
+
+    def r1cs_solver_load(self, r1cs_h, desc: "R1csSolverDesc"):
+        h = C.c_void_p()
+        self._check(self.lib.zkmi_r1cs_solver_load(self.h, r1cs_h, C.byref(desc), C.byref(h)),
+                    "zkmi_r1cs_solver_load")
+        return h
+
+    def r1cs_solver_free(self, h):
+        self.lib.zkmi_r1cs_solver_free(self.h, h)
+
+    def r1cs_solver_info(self, h):
+        arr = (C.c_uint64 * 8)()
+        self._check(self.lib.zkmi_r1cs_solver_info(h, arr), "zkmi_r1cs_solver_info")
+        return dict(zip(("n_instr", "lanes_per_proof", "n_terms", "longest", "n_inversions",
+                         "n_wires", "n_constraints", "n_inputs"), [int(x) for x in arr]))
+
+    def r1cs_solve_batch(self, solver_h, inputs, batch, wires_out=None, abc_out=None,
+                         status_out=None):
+        if status_out is None:
+            status_out = np.zeros(batch, dtype=np.int32)
+        self._check(self.lib.zkmi_r1cs_solve_batch(self.h, solver_h, _ptr(inputs), batch,
+                                                   _ptr(wires_out), _ptr(abc_out),
+                                                   _ptr(status_out)), "zkmi_r1cs_solve_batch")
+        return status_out
+
+    def prove_r1cs_submit(self, pk_h, solver_h, inputs, batch, rs):
+        self._check(self.lib.zkmi_prove_r1cs_submit(self.h, pk_h, solver_h, _ptr(inputs), batch,
+                                                    _ptr(rs)), "zkmi_prove_r1cs_submit")
 
     def host_alloc(self, shape, dtype=np.uint64):
         """numpy array over page-locked memory from zkmi_host_alloc (free with host_free)."""

@@ -322,6 +322,60 @@ int zkmi_prove_witness_batch(zkmi_ctx* ctx, const zkmi_pk* pk, const void* wires
                              const void* b, const void* c, size_t n_constraints, size_t batch,
                              const void* rs, void* proofs_out);
 
+/* -- the gnark drop-in entry: solve AND prove from inputs --------------------------------------- */
+/* For a caller that holds a gnark ccs and no witness program (zkmi_cs): the GPU solves the
+ * gnark-shaped system itself, in place of cs.Solve on the caller's CPUs.  The description adds
+ * to the loaded matrices what gnark's solver walks [UPSTREAM-RECALL]: the instruction order
+ * (cs.Instructions: constraints and hint calls interleaved) and the hint table.  The caller names no
+ * solve wire: as gnark does at run time, the library finds the one wire of each constraint that no
+ * earlier instruction has solved (ONE, the public and the secret inputs are solved to begin with).
+ * Hints are named by kind number; a shim maps gnark's hint names to them.  Supported kinds: */
+enum zkmi_hint_kind {
+  ZKMI_HINT_INVZERO = 1, /* solver.InvZeroHint: one input x, one output 1/x, or 0 for x = 0 */
+  ZKMI_HINT_NBITS = 2    /* bits.NBits: one input, output i = bit i of its canonical value */
+};
+/* Every other kind (3 limbs, 4 lookup multiplicities, 5 commitment, 6 byte operations, 7 emulated
+ * product: the numbers of this repository's frontend) is refused by name at load time. */
+typedef struct {
+  uint32_t n_public;  /* public wires including ONE */
+  uint32_t n_secret;
+  uint32_t n_instr, n_hints;
+  const uint32_t* instr;        /* n_instr x 2: (0 = constraint | 1 = hint, index), in solve order;
+                                   every constraint exactly once */
+  const uint32_t* hint_kind;    /* n_hints */
+  const uint32_t* hint_in_ptr;  /* n_hints + 1: hint h reads the expressions hint_in_ptr[h] .. [h + 1] */
+  const uint32_t* hint_lc_ptr;  /* one more than expressions: offsets into hint_terms */
+  const zkmi_term* hint_terms;  /* coefficient indices into the loaded system's table */
+  const uint32_t* hint_out_ptr; /* n_hints + 1 offsets into hint_out */
+  const uint32_t* hint_out;     /* wires the hints write */
+  uint32_t lanes_per_proof;     /* lanes of a wavefront that share one proof's terms: a power of two,
+                                   1 .. 64; 0 = the power of two in 1 .. 16 nearest to the mean number
+                                   of terms per instruction */
+} zkmi_r1cs_solver_desc;
+typedef struct zkmi_r1cs_solver zkmi_r1cs_solver;
+/* Builds the solve plan on the host (csrc/r1cs_plan.h) and uploads it; `r1cs` and the host arrays
+ * may be freed afterwards.  ZKMI_ERR_ARG with a message that names the instruction when a
+ * constraint has two unknown wires, its unknown occurs twice, a hint reads an unsolved wire, an
+ * index is out of range, a constraint occurs twice or never, a wire stays unsolved, or a hint is of
+ * an unsupported kind. */
+int zkmi_r1cs_solver_load(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const zkmi_r1cs_solver_desc* desc,
+                          zkmi_r1cs_solver** out);
+void zkmi_r1cs_solver_free(zkmi_ctx* ctx, zkmi_r1cs_solver* solver);
+/* info[0] = instructions, [1] = lanes per proof, [2] = terms of all instructions (the unknowns'
+ * own excluded), [3] = terms of the longest instruction, [4] = field inversions per proof,
+ * [5] = n_wires, [6] = n_constraints, [7] = inputs per proof (n_public - 1 + n_secret). */
+int zkmi_r1cs_solver_info(const zkmi_r1cs_solver* solver, uint64_t* info /* 8 */);
+/* Witness solve only, the conventions of zkmi_solve_batch: inputs batch x (n_public - 1 + n_secret),
+ * wires_out (optional) batch x n_wires, abc_out (optional) 3 x batch x n_constraints, status_out per
+ * proof 0 or ZKMI_ERR_UNSATISFIED (an assertion fails, or the factor a solve divides by is 0). */
+int zkmi_r1cs_solve_batch(zkmi_ctx* ctx, const zkmi_r1cs_solver* solver, const void* inputs,
+                          size_t batch, void* wires_out, void* abc_out, int32_t* status_out);
+/* Stage 1 of a prove from inputs; the matching zkmi_prove_collect returns the proofs.  Pipelines
+ * exactly like zkmi_prove_submit (two batches in flight, same streams, same HBM plan).  Keys with
+ * commitments are refused before anything is queued. */
+int zkmi_prove_r1cs_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_solver* solver,
+                           const void* inputs, size_t batch, const void* rs);
+
 /* -- PLONK (BASELINE config 5 names this backend) ----------------------------------------------- */
 /* Stands in for plonk.Prove of gnark backend/plonk/bn254 [UPSTREAM-RECALL]: KZG commitments over
  * the SRS, blinded wire polynomials, permutation grand product, quotient on the coset 5<w_4n>

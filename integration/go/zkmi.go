@@ -20,6 +20,11 @@
 //
 // Submit(k+1) before Collect(k) overlaps batch k+1's CPU solve and PCIe transfer with batch k's
 // MSM kernels (two batches in flight, as zkmi_prove_submit).
+//
+// Without gnark's solver: LoadSolver(ccs) uploads the instruction order and the hint table of the
+// ccs (zkmi_r1cs_solver_load), SubmitInputs ships the public and secret inputs only and the GPU
+// solves (zkmi_prove_r1cs_submit; tests/test_gpu_r1cs_solver.py drives that sequence).  Hints
+// solver.InvZeroHint and bits.NBits only; everything else, and keys with commitments, is refused.
 package zkmi
 
 /*
@@ -43,6 +48,7 @@ import (
 	"github.com/consensys/gnark/backend/witness"
 	"github.com/consensys/gnark/constraint"
 	cs_bn254 "github.com/consensys/gnark/constraint/bn254"
+	"github.com/consensys/gnark/constraint/solver"
 )
 
 // Device owns one zkmi context (one per GPU).  A context is thread-compatible: calls are
@@ -193,6 +199,92 @@ func (d *Device) LoadR1CS(ccs *cs_bn254.R1CS) (*R1CS, error) {
 	return &R1CS{h: h, nConstraints: len(r1cs)}, nil
 }
 
+// Solver is the device-resident solve plan of the ccs (zkmi_r1cs_solver_load).
+type Solver struct {
+	h       *C.zkmi_r1cs_solver
+	nInputs int
+}
+
+// hintKinds maps gnark's hint names to the kind numbers of include/zkmi.h.  The names are what
+// solver.GetHintName returns for solver.InvZeroHint and bits.NBits [UPSTREAM-RECALL: unpinned].
+var hintKinds = map[string]uint32{
+	"github.com/consensys/gnark/constraint/solver.InvZeroHint": C.ZKMI_HINT_INVZERO,
+	"github.com/consensys/gnark/std/math/bits.NBits":           C.ZKMI_HINT_NBITS,
+}
+
+// LoadSolver walks ccs.Instructions in order [UPSTREAM-RECALL: constraint.System{Instructions,
+// Blueprints}, PackedInstruction.Unpack, BlueprintHint.DecompressHint, HintMapping{HintID, Inputs,
+// OutputRange}] and describes them as zkmi_r1cs_solver_desc does: (0, constraint index) for every
+// R1C, in the order GetR1Cs enumerates them, and (1, hint index) with the hint's input expressions
+// and output wires.  A hint that is neither InvZero nor NBits gets kind 0 here, which the library
+// refuses by instruction.  r1cs is the handle of LoadR1CS for the same ccs.
+func (d *Device) LoadSolver(ccs *cs_bn254.R1CS, r1cs *R1CS, lanesPerProof int) (*Solver, error) {
+	names := make(map[solver.HintID]string)
+	for id, name := range ccs.MHintsDependencies {
+		names[id] = name
+	}
+	var instr, kinds, outs []uint32
+	inPtr, lcPtr, outPtr := []uint32{0}, []uint32{0}, []uint32{0}
+	var terms []C.zkmi_term
+	nextR1C := uint32(0)
+	for _, pi := range ccs.Instructions {
+		inst := pi.Unpack(&ccs.System)
+		switch bp := ccs.Blueprints[pi.BlueprintID].(type) {
+		case constraint.BlueprintR1C:
+			instr = append(instr, 0, nextR1C)
+			nextR1C++
+		case constraint.BlueprintHint:
+			var hm constraint.HintMapping
+			bp.DecompressHint(&hm, inst)
+			instr = append(instr, 1, uint32(len(kinds)))
+			kinds = append(kinds, hintKinds[names[hm.HintID]]) // 0 when unsupported
+			for _, le := range hm.Inputs {
+				for _, t := range le {
+					terms = append(terms, C.zkmi_term{coeff: C.uint32_t(t.CID), wire: C.uint32_t(t.VID)})
+				}
+				lcPtr = append(lcPtr, uint32(len(terms)))
+			}
+			inPtr = append(inPtr, uint32(len(lcPtr)-1))
+			for w := hm.OutputRange.Start; w < hm.OutputRange.End; w++ {
+				outs = append(outs, w)
+			}
+			outPtr = append(outPtr, uint32(len(outs)))
+		default:
+			return nil, errors.New("zkmi: an instruction that is neither an R1C nor a hint")
+		}
+	}
+	desc := (*C.zkmi_r1cs_solver_desc)(C.calloc(1, C.size_t(unsafe.Sizeof(C.zkmi_r1cs_solver_desc{}))))
+	defer C.free(unsafe.Pointer(desc))
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	u32 := func(x []uint32) *C.uint32_t {
+		if len(x) == 0 {
+			return nil
+		}
+		pin.Pin(&x[0])
+		return (*C.uint32_t)(unsafe.Pointer(&x[0]))
+	}
+	desc.n_public = C.uint32_t(ccs.GetNbPublicVariables()) // counts the ONE wire
+	desc.n_secret = C.uint32_t(ccs.GetNbSecretVariables())
+	desc.n_instr, desc.n_hints = C.uint32_t(len(instr)/2), C.uint32_t(len(kinds))
+	desc.instr, desc.hint_kind = u32(instr), u32(kinds)
+	desc.hint_in_ptr, desc.hint_lc_ptr, desc.hint_out_ptr, desc.hint_out = u32(inPtr), u32(lcPtr), u32(outPtr), u32(outs)
+	if len(terms) > 0 {
+		pin.Pin(&terms[0])
+		desc.hint_terms = (*C.zkmi_term)(unsafe.Pointer(&terms[0]))
+	}
+	desc.lanes_per_proof = C.uint32_t(lanesPerProof) // 0 = auto
+	d.mu.Lock()
+	defer d.mu.Unlock()
+	var h *C.zkmi_r1cs_solver
+	if rc := C.zkmi_r1cs_solver_load(d.ctx, r1cs.h, desc, &h); rc != 0 {
+		return nil, d.lastError()
+	}
+	return &Solver{h: h, nInputs: ccs.GetNbPublicVariables() - 1 + ccs.GetNbSecretVariables()}, nil
+}
+
+func (d *Device) FreeSolver(s *Solver) { C.zkmi_r1cs_solver_free(d.ctx, s.h) }
+
 // Prover pipelines batches of one circuit: two page-locked wire arrays, two batches in flight.
 type Prover struct {
 	d     *Device
@@ -268,6 +360,30 @@ func (pr *Prover) Submit(ws []witness.Witness, rs []fr.Element, opts ...backend.
 		return pr.d.lastError()
 	}
 	pr.slot ^= 1
+	pr.sizes = append(pr.sizes, batch)
+	return nil
+}
+
+// SubmitInputs queues a batch that the GPU solves itself: inputs holds, per proof, the public
+// values (without ONE) and then the secret values, as witness.Vector() orders them.  No goroutine
+// runs ccs.Solve.  Collect returns the proofs; a proof whose inputs do not satisfy the system has
+// status ZKMI_ERR_UNSATISFIED.
+func (pr *Prover) SubmitInputs(s *Solver, inputs []fr.Element, rs []fr.Element) error {
+	if s.nInputs == 0 || len(inputs)%s.nInputs != 0 || len(rs) != 2*(len(inputs)/s.nInputs) {
+		return errors.New("inputs must hold nbPublic - 1 + nbSecret values and rs 2 scalars per proof")
+	}
+	batch := len(inputs) / s.nInputs
+	var pin runtime.Pinner
+	pin.Pin(&inputs[0])
+	pin.Pin(&rs[0])
+	defer pin.Unpin() // pageable host memory: consumed before the call returns
+	pr.d.mu.Lock()
+	rc := C.zkmi_prove_r1cs_submit(pr.d.ctx, pr.key.h, s.h, unsafe.Pointer(&inputs[0]), C.size_t(batch),
+		unsafe.Pointer(&rs[0]))
+	pr.d.mu.Unlock()
+	if rc != 0 {
+		return pr.d.lastError()
+	}
 	pr.sizes = append(pr.sizes, batch)
 	return nil
 }

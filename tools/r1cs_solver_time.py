@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""Times the gnark-shaped solver (zkmi_r1cs_solve_batch / zkmi_prove_r1cs_submit) on the benched
+circuit, smt_inclusion_circuit(160) x 1024 proofs with 10 populated siblings, next to the frontend
+program's solver (zkmi_solve_batch / zkmi_prove_submit) as the yardstick.  Prints one JSON line.
+
+    python tools/r1cs_solver_time.py [--out FILE]
+
+Three GPU steps, each a child process of its own under its own time limit; the first step that fails
+ends the run (nothing more is started on the GPU):
+  solve        idle-chip milliseconds of one solve of the batch, inputs resident in HBM, no outputs
+               copied back: the gnark-shaped solver at the automatic lane count and at 8, 16, 32
+               lanes per proof, then the frontend program.  Host clock around calls that end in a
+               stream synchronise; one warm-up call, then the median and the least of five.
+  pipe-program pipelined proofs/s of submit + collect over --steps batches (two in flight)
+  pipe-r1cs    the same through submit_r1cs
+"""
+import argparse
+import json
+import os
+import random
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+LEVELS, POPULATED, BATCH, DISTINCT = 160, 10, 1024, 64
+STEP_LIMIT_S = {"solve": 240, "pipe-program": 240, "pipe-r1cs": 300}
+
+
+def _setup(need_key):
+    import numpy as np
+    import torch  # noqa: F401  (before the library: one HIP runtime per process)
+    from gnark_crypto_primitives_amd import circuits, groth16, lib
+    from gnark_crypto_primitives_amd.frontend import compile_circuit
+    from gnark_crypto_primitives_amd.frontend.compile import to_mont_array
+    from gnark_crypto_primitives_amd.tree import smt_witness
+    ctx = lib.Context(0)
+    cc = compile_circuit(circuits.smt_inclusion_circuit(LEVELS))
+    rng = random.Random(160)
+    distinct = [to_mont_array(cc.assignment_vector(
+        smt_witness.synthetic_inclusion(rng, LEVELS, POPULATED))) for _ in range(DISTINCT)]
+    inp = np.stack([distinct[i % DISTINCT] for i in range(BATCH)])
+    rs = np.stack([to_mont_array([rng.randrange(groth16.R), rng.randrange(groth16.R)])
+                   for _ in range(BATCH)])
+    # the solve step needs no proving key worth its tables: the narrowest windows load fastest
+    pk, _, _ = groth16.setup(cc, 1, groth16.gpu_mul(ctx))
+    prover = groth16.Prover(ctx, cc, pk, *((0, 0) if need_key else (4, 4)), max_batch=BATCH)
+    dev = torch.device("cuda:0")
+    inp_d = torch.from_numpy(inp.view(np.int64)).to(dev)
+    rs_d = torch.from_numpy(rs.view(np.int64)).to(dev)
+    torch.cuda.synchronize()
+    return ctx, cc, prover, inp_d, rs_d
+
+
+def _time_ms(fn, repeats=5):
+    fn()                                    # warm-up: code objects, scratch buffers
+    ms = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        fn()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "runs": repeats}
+
+
+def step_solve():
+    import numpy as np
+    ctx, cc, prover, inp_d, _ = _setup(False)
+    status = np.zeros(BATCH, np.int32)
+    out = {"instr": None, "r1cs": {}}
+    for lanes in (0, 8, 16, 32):
+        h = prover.load_r1cs_solver(lanes)
+        info = ctx.r1cs_solver_info(h)
+        out["instr"] = {k: info[k] for k in ("n_instr", "n_terms", "longest", "n_inversions")}
+        t = _time_ms(lambda: ctx.r1cs_solve_batch(h, inp_d, BATCH, None, None, status))
+        assert not status.any()
+        out["r1cs"]["auto" if lanes == 0 else str(lanes)] = dict(t, lanes_per_proof=info["lanes_per_proof"])
+    t = _time_ms(lambda: ctx.solve_batch(prover.cs_h, inp_d, BATCH, None, None, status))
+    assert not status.any()
+    out["program"] = dict(t, lanes_per_proof=cc.lanes_per_proof)
+    out["ratio_auto_to_program"] = out["r1cs"]["auto"]["median_ms"] / t["median_ms"]
+    prover.close()
+    return out
+
+
+def step_pipe(which, steps):
+    ctx, cc, prover, inp_d, rs_d = _setup(True)
+    submit = prover.submit if which == "program" else prover.submit_r1cs
+    if which == "r1cs":
+        prover.load_r1cs_solver(0)
+
+    def run(n):
+        submit(inp_d, rs_d)
+        for _ in range(n - 1):
+            submit(inp_d, rs_d)
+            _, st = prover.collect()
+            assert not st.any()
+        _, st = prover.collect()
+        assert not st.any()
+        return ctx.last_timings()
+    run(3)
+    t0 = time.perf_counter()
+    timings = run(steps)
+    dt = time.perf_counter() - t0
+    prover.close()
+    return {"proofs_per_s": steps * BATCH / dt, "ms_per_step": dt / steps * 1e3, "steps": steps,
+            "solve_stage_ms_last_batch": timings[0]}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--step", choices=tuple(STEP_LIMIT_S), help="run one step in this process")
+    ap.add_argument("--steps", type=int, default=12, help="batches of a pipelined step (at least 10)")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    args = ap.parse_args()
+    if args.steps < 10:
+        ap.error("--steps must be at least 10")
+    if args.step:
+        res = step_solve() if args.step == "solve" else step_pipe(args.step[5:], args.steps)
+        print("RESULT " + json.dumps(res), flush=True)
+        return 0
+    result = {"circuit": f"smt_inclusion_circuit({LEVELS})", "batch": BATCH, "populated": POPULATED}
+    rc = 0
+    for step, limit in STEP_LIMIT_S.items():
+        # a fresh child per step; killed at its limit; after a failure nothing more runs on the GPU
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", step,
+                                "--steps", str(args.steps)], capture_output=True, text=True, timeout=limit)
+        except subprocess.TimeoutExpired:
+            result[step] = {"error": f"time limit of {limit} s"}
+            rc = 1
+            break
+        lines = [x for x in p.stdout.splitlines() if x.startswith("RESULT ")]
+        if p.returncode != 0 or not lines:
+            result[step] = {"error": f"exit status {p.returncode}", "stderr": p.stderr[-2000:]}
+            rc = 1
+            break
+        result[step] = json.loads(lines[-1][7:])
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main())
