@@ -196,6 +196,7 @@ int commit_keys_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk* pk) {
       ctx->err = "pk: commitment " + std::to_string(i) + " holds a wire index out of range";
       return ZKMI_ERR_ARG;
     }
+    ck.priv = priv;
     if (c.n_private) {
       ZK_HIP(hipMalloc((void**)&ck.private_dev, (size_t)c.n_private * 4));
       ZK_HIP(hipMemcpy(ck.private_dev, priv.data(), (size_t)c.n_private * 4, hipMemcpyHostToDevice));

@@ -17,7 +17,15 @@
 //               RK_SOLVE_L   ... in L: x = (c / b - a) / k, b = 0 is unsatisfied   (RK_SOLVE_R alike)
 //               RK_INVZERO   hint: target = 1 / a, 0 for a = 0       (a = the hint's input expression)
 //               RK_NBITS     hint: bit i of the canonical value of a into wire outs[target + i]
-//     target    the wire solved (RK_NBITS: the first entry of the hint's output wires in `outs`)
+//             plans of ZKMI_HINTS_STD only (P.ext says whether a plan holds one; none has an a/b/c row):
+//               RK_LIMBS     hint: bits [i coef, (i + 1) coef) of the canonical value of a into wire
+//                            outs[target + i], i < k: RK_NBITS with a width, 1 .. 64
+//               RK_BYTEOP    hint: target = low 32 bits of a  XOR (coef = 1) | AND (coef = 2)  those of b
+//               RK_COUNT_BEGIN / RK_COUNT_Q / RK_COUNT_END   the lookup-multiplicity hint, see below
+//               RK_COMMIT    the commitment hint: a phase boundary, never executed -- a launch ends
+//                            in front of it and the host supplies wire `target` (P.commits)
+//     target    the wire solved (RK_NBITS, RK_LIMBS, RK_COUNT_*: the first entry of the hint's output
+//               wires in `outs`)
 //     coef      RK_SOLVE_*: coefficient word of the unknown (as in the terms below)
 //     coef_inv  RK_SOLVE_*: index of 1 / k, appended to the coefficient table (inverted here, once)
 //   quad 1  (first term, product rows, unit rows, k)
@@ -27,15 +35,25 @@
 //     +1 / -1, padded likewise -- a row is one term per sub-lane, so the S sub-lanes of a proof never
 //     diverge inside a row.  k = constraint row the a, b, c of the instruction go to (RK_NBITS: the
 //     number of output wires).
+// The lookup-multiplicity hint (one instruction) is a run of records: RK_COUNT_BEGIN (no terms; the
+//   sub-lanes zero the k = table size counters, the low words of wires outs[target ..]), then
+//   RK_COUNT_Q steps of up to S queries, one per sub-lane: term row r of sub-lane s is term r of
+//   query s of the step, padded to the step's longest query, so a sub-lane's own sum is its query and
+//   nothing is added across sub-lanes; all rows are product rows (a unit coefficient multiplies by
+//   1), k = queries in the step (sub-lanes from k on hold none), coef = table size; then
+//   RK_COUNT_END (no terms; the sub-lanes turn the k counters into field images in place).
 // Term = (wire | tag << 30, coefficient index | unit << 30): tag RT_L / RT_R / RT_O names the
-//   expression the term belongs to (hints: RT_L), RT_PAD a padding term (wire 0, adds nothing);
+//   expression the term belongs to (hints: RT_L; RK_BYTEOP: RT_L and RT_R), RT_PAD a padding term
+//   (wire 0, adds nothing);
 //   unit 1 / 2 = the coefficient is +1 / -1, as zkmi_r1cs_load marks it.
 // The term array ends with R1CS_TERM_SLACK rows of padding terms and the records with one RK_ASSERT
-// record without terms: the kernel fetches three rows and one record ahead of what it runs.
+// record without terms: the kernel fetches three rows and one record ahead of what it runs.  Records
+// and terms are contiguous, so a launch may run any range [begin, end) of the records.
 //
 // Every count the kernel loops over and every index it uses as an address comes out of
 // r1cs_plan_build, which has checked it: that is what bounds the kernel's accesses and its run time.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -46,7 +64,10 @@
 
 namespace zk {
 
-enum { RK_ASSERT = 0, RK_SOLVE_O, RK_SOLVE_L, RK_SOLVE_R, RK_INVZERO, RK_NBITS };
+enum {
+  RK_ASSERT = 0, RK_SOLVE_O, RK_SOLVE_L, RK_SOLVE_R, RK_INVZERO, RK_NBITS,
+  RK_LIMBS, RK_BYTEOP, RK_COUNT_BEGIN, RK_COUNT_Q, RK_COUNT_END, RK_COMMIT
+};
 enum { RT_L = 0, RT_R = 1, RT_O = 2, RT_PAD = 3 };
 constexpr uint32_t R1CS_IDX_MASK = 0x3fffffffu;   // low 30 bits of a term word
 constexpr uint32_t R1CS_TERM_SLACK = 3;           // rows of padding terms behind the last instruction
@@ -67,12 +88,19 @@ struct R1csPlanIn {
   const R1csTerm* terms[3] = {};
   const zkmi_r1cs_solver_desc* desc = nullptr;   // host arrays
 };
+// A commitment hint: the record a launch stops in front of, and what the proving key must agree with
+struct R1csCommit {
+  uint32_t instr = 0, record = 0, wire = 0;
+  std::vector<uint32_t> hashed, priv;
+};
 struct R1csPlan {
   uint32_t S = 0, n_instr = 0;
-  std::vector<R1csRecord> records;   // n_instr + 1
+  bool ext = false;                  // holds a record kind from RK_LIMBS on
+  std::vector<R1csRecord> records;   // one per instruction (a lookup-multiplicity hint: several) + 1
+  std::vector<R1csCommit> commits;   // in instruction order
   std::vector<R1csTerm> terms;       // plan terms: (wire | tag << 30, coef)
   std::vector<Fr> coeffs;            // the system's table, then the inverses (2^261 images)
-  std::vector<uint32_t> outs;        // output wires of the RK_NBITS hints
+  std::vector<uint32_t> outs;        // output wires of the RK_NBITS, RK_LIMBS and RK_COUNT_* hints
   uint64_t n_terms = 0;              // known terms, without padding
   uint32_t longest = 0;              // most known terms in one instruction
   uint32_t n_inversions = 0;         // RK_SOLVE_L + RK_SOLVE_R + RK_INVZERO
@@ -97,6 +125,23 @@ inline const char* r1cs_hint_name(uint32_t kind) {
   return kind < 8 ? names[kind] : "of an unknown kind";
 }
 
+// bits [pos, pos + wd) of the 256-bit integer v, wd in 1 .. 64; the bits from 256 on are 0
+ZK_HD uint64_t r1cs_limb(const Fr& v, uint32_t pos, uint32_t wd) {
+  if (pos >= 256) return 0;
+  const uint32_t i = pos >> 5, sh = pos & 31;
+  const uint64_t two = (uint64_t)(i < 7 ? v.v[i + 1] : 0u) << 32 | v.v[i];
+  uint64_t r = two >> sh;
+  if (sh && i < 6) r |= (uint64_t)v.v[i + 2] << (64 - sh);
+  return wd >= 64 ? r : r & (((uint64_t)1 << wd) - 1);
+}
+// the 2^256 image of an integer below 2^64
+ZK_HD Fr r1cs_small(uint64_t x) {
+  Fr m = Fr::zero();
+  m.v[0] = (uint32_t)x;
+  m.v[1] = (uint32_t)(x >> 32);
+  return to_mont(m);
+}
+
 // Returns the empty string and the plan, or what is wrong with the description.
 inline std::string r1cs_plan_build(const R1csPlanIn& in, R1csPlan* out) {
   const zkmi_r1cs_solver_desc& d = *in.desc;
@@ -105,6 +150,8 @@ inline std::string r1cs_plan_build(const R1csPlanIn& in, R1csPlan* out) {
     return pre + "the system needs 1 .. 2^30 - 1 wires and coefficients";
   uint32_t S = d.lanes_per_proof;
   if (S > 64 || (S & (S - 1))) return pre + "lanes_per_proof must be 0 (auto) or a power of two, 1 .. 64";
+  if (d.hint_set != ZKMI_HINTS_BASIC && d.hint_set != ZKMI_HINTS_STD)
+    return pre + "hint_set must be ZKMI_HINTS_BASIC (0) or ZKMI_HINTS_STD (1)";
   if (d.n_public == 0 || (uint64_t)d.n_public + d.n_secret > in.n_wires)
     return pre + "n_public (which counts the ONE wire) + n_secret must be in 1 .. n_wires";
   if (d.n_instr == 0 || !d.instr) return pre + "no instructions";
@@ -154,7 +201,13 @@ inline std::string r1cs_plan_build(const R1csPlanIn& in, R1csPlan* out) {
   struct Pending {
     uint32_t kind, target, coef, k;
     std::vector<R1csTerm> mul, unit;   // known terms, tagged
+    std::vector<std::vector<R1csTerm>> queries;   // RK_COUNT_BEGIN: the terms of every query
   };
+  std::vector<R1csCommit> commits;
+  bool ext = false;
+  // 2^251 is the Montgomery image of 2^-5: takes a sum of 2^261 images to gnark's image
+  Fr down5 = Fr::zero();
+  down5.v[7] = 1u << 27;
   std::vector<Pending> pend(d.n_instr);
   std::vector<uint32_t> outs;
   uint64_t n_terms = 0;
@@ -170,19 +223,85 @@ inline std::string r1cs_plan_build(const R1csPlanIn& in, R1csPlan* out) {
       if (idx >= d.n_hints) return at + ": hint index " + std::to_string(idx) + " out of range";
       const uint32_t hk = d.hint_kind[idx];
       const std::string hat = at + " (hint " + std::to_string(idx) + ")";
-      if (hk != ZKMI_HINT_INVZERO && hk != ZKMI_HINT_NBITS)
+      const bool std_kind = hk == ZKMI_HINT_LIMBS || hk == ZKMI_HINT_COUNT || hk == ZKMI_HINT_COMMIT ||
+                            hk == ZKMI_HINT_BYTEOP;
+      if (hk != ZKMI_HINT_INVZERO && hk != ZKMI_HINT_NBITS && !(d.hint_set == ZKMI_HINTS_STD && std_kind))
         return hat + ": hints " + r1cs_hint_name(hk) + " are not supported on this entry";
       const uint32_t in0 = d.hint_in_ptr[idx], in1 = d.hint_in_ptr[idx + 1];
       const uint32_t o0 = d.hint_out_ptr[idx], o1 = d.hint_out_ptr[idx + 1];
-      if (in1 != in0 + 1 || o1 == o0 || (hk == ZKMI_HINT_INVZERO && o1 != o0 + 1))
-        return hat + ": " + r1cs_hint_name(hk) + " takes one input" +
+      const uint32_t nin = in1 - in0, nout = o1 - o0;
+      const std::string name = r1cs_hint_name(hk);
+      if (!std_kind && (nin != 1 || nout == 0 || (hk == ZKMI_HINT_INVZERO && nout != 1)))
+        return hat + ": " + name + " takes one input" +
                (hk == ZKMI_HINT_INVZERO ? " and has one output" : " and has outputs");
-      for (uint32_t t = d.hint_lc_ptr[in0]; t < d.hint_lc_ptr[in0 + 1]; t++) {
-        const uint32_t cid = d.hint_terms[t].coeff, wire = d.hint_terms[t].wire;
-        if (cid >= in.n_coeffs || wire >= in.n_wires)
-          return hat + ": a term's coefficient or wire index is out of range";
-        if (!solved[wire]) return hat + ": reads wire " + std::to_string(wire) + ", which is not solved yet";
-        known(wire, cid | unit_of(cid) << 30, RT_L);
+      if (hk == ZKMI_HINT_LIMBS && (nin != 2 || nout == 0))
+        return hat + ": " + name + " takes a width and one input and has outputs";
+      if (hk == ZKMI_HINT_COUNT && (nin < 2 || nout == 0))
+        return hat + ": " + name + " takes a table size and queries and has outputs";
+      if (hk == ZKMI_HINT_BYTEOP && (nin != 3 || nout != 1))
+        return hat + ": " + name + " takes an operation and two inputs and has one output";
+      if (hk == ZKMI_HINT_COMMIT && (nin < 1 || nout != 1))
+        return hat + ": " + name + " takes the number of hashed operands and the operands and has one output";
+      // expression e of the hint: every term checked, then handed to `sink`
+      std::string bad;
+      auto expression = [&](uint32_t e, auto sink) {
+        for (uint32_t t = d.hint_lc_ptr[e]; bad.empty() && t < d.hint_lc_ptr[e + 1]; t++) {
+          const uint32_t cid = d.hint_terms[t].coeff, wire = d.hint_terms[t].wire;
+          if (cid >= in.n_coeffs || wire >= in.n_wires)
+            bad = hat + ": a term's coefficient or wire index is out of range";
+          else if (!solved[wire])
+            bad = hat + ": reads wire " + std::to_string(wire) + ", which is not solved yet";
+          else
+            sink(wire, cid);
+        }
+      };
+      uint32_t first_expr = in0, p0 = 0;
+      if (std_kind) {
+        // the constant parameter: terms on ONE alone, a value below 2^32
+        Fr sum = Fr::zero();
+        expression(in0, [&](uint32_t wire, uint32_t cid) {
+          if (wire != 0)
+            bad = hat + ": the parameter of " + name + " is not a constant (it reads wire " +
+                  std::to_string(wire) + ")";
+          sum = add(sum, in.coeffs[cid]);
+        });
+        if (!bad.empty()) return bad;
+        const Fr v = from_mont(mul(sum, down5));
+        p0 = (v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) ? 0xffffffffu : v.v[0];
+        first_expr = in0 + 1;
+      }
+      if (hk == ZKMI_HINT_LIMBS && (p0 < 1 || p0 > 64))
+        return hat + ": limb width " + std::to_string(p0) + " is outside 1 .. 64";
+      if (hk == ZKMI_HINT_COUNT && p0 != nout)
+        return hat + ": table size " + std::to_string(p0) + " is not the number of outputs, " +
+               std::to_string(nout);
+      if (hk == ZKMI_HINT_BYTEOP && p0 != 1 && p0 != 2)
+        return hat + ": byte operation " + std::to_string(p0) + " is neither 1 (XOR) nor 2 (AND)";
+      if (hk == ZKMI_HINT_COMMIT && p0 > nin - 1)
+        return hat + ": " + std::to_string(p0) + " hashed operands among " + std::to_string(nin - 1);
+      R1csCommit com;
+      for (uint32_t e = first_expr; e < in1; e++) {
+        const uint32_t j = e - first_expr;
+        if (hk == ZKMI_HINT_COUNT) {
+          p.queries.emplace_back();
+          expression(e, [&](uint32_t wire, uint32_t cid) {
+            p.queries.back().push_back(R1csTerm{wire | (uint32_t)RT_L << 30, cid});
+          });
+          n_terms += p.queries.back().size();
+          if (p.queries.back().size() > longest) longest = (uint32_t)p.queries.back().size();
+        } else if (hk == ZKMI_HINT_COMMIT) {
+          // commit_phase reads wire rows, not expressions
+          uint32_t n = 0, w = 0, c = 0;
+          expression(e, [&](uint32_t wire, uint32_t cid) { n++, w = wire, c = cid; });
+          if (bad.empty() && (n != 1 || in.coeffs[c] != one32))
+            return hat + ": commitment operand " + std::to_string(j) +
+                   " is not a single wire with coefficient 1";
+          (j < p0 ? com.hashed : com.priv).push_back(w);
+        } else {
+          const uint32_t tag = hk == ZKMI_HINT_BYTEOP && j == 1 ? RT_R : RT_L;
+          expression(e, [&](uint32_t wire, uint32_t cid) { known(wire, cid | unit_of(cid) << 30, tag); });
+        }
+        if (!bad.empty()) return bad;
       }
       for (uint32_t o = o0; o < o1; o++) {
         const uint32_t wire = d.hint_out[o];
@@ -190,17 +309,27 @@ inline std::string r1cs_plan_build(const R1csPlanIn& in, R1csPlan* out) {
         if (solved[wire]) return hat + ": output wire " + std::to_string(wire) + " is already solved";
         solved[wire] = 1;
       }
-      if (hk == ZKMI_HINT_INVZERO) {
-        p.kind = RK_INVZERO;
+      ext = ext || std_kind;
+      p.coef = 0;
+      if (hk == ZKMI_HINT_INVZERO || hk == ZKMI_HINT_BYTEOP) {
+        p.kind = hk == ZKMI_HINT_INVZERO ? RK_INVZERO : RK_BYTEOP;
         p.target = d.hint_out[o0];
         p.k = 0;
+        if (hk == ZKMI_HINT_BYTEOP) p.coef = p0;
+      } else if (hk == ZKMI_HINT_COMMIT) {
+        p.kind = RK_COMMIT;
+        p.target = d.hint_out[o0];
+        p.k = (uint32_t)commits.size();
+        com.instr = ii;
+        com.wire = p.target;
+        commits.push_back(std::move(com));
       } else {
-        p.kind = RK_NBITS;
+        p.kind = hk == ZKMI_HINT_NBITS ? RK_NBITS : hk == ZKMI_HINT_LIMBS ? RK_LIMBS : RK_COUNT_BEGIN;
         p.target = (uint32_t)outs.size();
-        p.k = o1 - o0;
+        p.k = nout;
+        if (hk == ZKMI_HINT_LIMBS) p.coef = p0;
         outs.insert(outs.end(), d.hint_out + o0, d.hint_out + o1);
       }
-      p.coef = 0;
     } else if (ik == 0) {
       if (idx >= in.n_constraints) return at + ": constraint index " + std::to_string(idx) + " out of range";
       const std::string cat = at + " (constraint " + std::to_string(idx) + ")";
@@ -254,6 +383,8 @@ inline std::string r1cs_plan_build(const R1csPlanIn& in, R1csPlan* out) {
   P.n_terms = n_terms;
   P.longest = longest;
   P.outs = std::move(outs);
+  P.ext = ext;
+  P.commits = std::move(commits);
   P.coeffs.assign(in.coeffs, in.coeffs + in.n_coeffs);
   P.records.reserve((size_t)d.n_instr + 1);
   const R1csTerm pad{(uint32_t)RT_PAD << 30, 0};
@@ -267,6 +398,27 @@ inline std::string r1cs_plan_build(const R1csPlanIn& in, R1csPlan* out) {
   for (uint32_t ii = 0; ii < d.n_instr; ii++) {
     Pending& p = pend[ii];
     R1csRecord r{p.kind, p.target, p.coef, 0, 0, 0, 0, p.k};
+    if (p.kind == RK_COMMIT) P.commits[p.k].record = (uint32_t)P.records.size();
+    if (p.kind == RK_COUNT_BEGIN) {
+      // begin, the query steps of S queries each (one per sub-lane, term row by term row), end
+      r.first = (uint32_t)P.terms.size();
+      P.records.push_back(r);
+      for (size_t q0 = 0; q0 < p.queries.size(); q0 += S) {
+        const size_t nq = std::min<size_t>(S, p.queries.size() - q0);
+        size_t rows = 0;
+        for (size_t q = 0; q < nq; q++) rows = std::max(rows, p.queries[q0 + q].size());
+        const uint64_t first = P.terms.size();
+        if (first + (uint64_t)(rows + R1CS_TERM_SLACK) * S > 0xffffffffull) return pre + "more than 2^32 plan terms";
+        P.records.push_back(R1csRecord{RK_COUNT_Q, p.target, p.k, 0, (uint32_t)first, (uint32_t)rows, 0,
+                                       (uint32_t)nq});
+        P.terms.resize(first + rows * S, pad);
+        for (size_t q = 0; q < nq; q++)
+          for (size_t t = 0; t < p.queries[q0 + q].size(); t++) P.terms[first + t * S + q] = p.queries[q0 + q][t];
+      }
+      P.records.push_back(R1csRecord{RK_COUNT_END, p.target, 0, 0, (uint32_t)P.terms.size(), 0, 0, p.k});
+      p.queries = std::vector<std::vector<R1csTerm>>();
+      continue;
+    }
     if (p.kind == RK_SOLVE_O || p.kind == RK_SOLVE_L || p.kind == RK_SOLVE_R) {
       r.coef_inv = (uint32_t)P.coeffs.size();
       P.coeffs.push_back(inverse_261(in.coeffs[p.coef & R1CS_IDX_MASK]));

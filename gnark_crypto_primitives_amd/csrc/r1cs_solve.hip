@@ -17,6 +17,8 @@
 // There is no CPU fallback in this file.
 #include <algorithm>
 #include <new>
+#include <string>
+#include <vector>
 
 #include "zkmi_internal.h"
 #include "ff29.h"
@@ -27,6 +29,9 @@ using namespace zk;
 
 struct zkmi_r1cs_solver {
   uint32_t n_wires = 0, n_constraints = 0, n_inputs = 0, n_instr = 0, S = 1;
+  uint32_t n_records = 0;             // what the kernel walks: n_instr, or more with lookup hints
+  bool ext = false;                   // the plan holds a record kind of ZKMI_HINTS_STD
+  std::vector<R1csCommit> commits;    // host: the commitment hints, the launches' boundaries
   uint32_t longest = 0, n_inversions = 0;
   uint64_t n_terms = 0;
   // device: the plan (r1cs_plan.h)
@@ -68,8 +73,15 @@ __device__ __forceinline__ Fr sum_sublanes(Fr v) {
 // and coefficients are fetched three and two rows ahead of the row in work, across instruction
 // ends.  A wire value fetched ahead of the store that writes it is replaced in registers (the bits
 // of an NBits hint: fetched again), so no instruction waits for its predecessor's store.
+// A launch runs the records [begin, end): records and terms are contiguous and end in the slack the
+// plan appends, so the fetches start at records[begin] and run ahead of `end` like anywhere else.
+// EXT = the plan holds record kinds of ZKMI_HINTS_STD (limbs, byte operations, lookup
+// multiplicities); plans without one run the EXT = false instance, which holds none of their code.
+// A lookup hint counts with an atomic add on the low word of the counter's wire slot and reads back
+// with the same scope, as the CLS_HIST branch of solve_vliw_kernel (solve.hip) does: the sub-lanes of
+// a proof share the counters.
 // All counts and indices come from a plan that r1cs_plan_build has checked.
-template <int S>
+template <int S, bool EXT>
 __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict__ recs,
                                                         const uint2* __restrict__ terms,
                                                         const Fr* __restrict__ coeffs,
@@ -77,26 +89,27 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
                                                         Fr* __restrict__ a, Fr* __restrict__ b,
                                                         Fr* __restrict__ c,
                                                         int32_t* __restrict__ status, size_t Bp,
-                                                        uint32_t n_instr) {
+                                                        uint32_t begin, uint32_t end) {
   constexpr int PPW = 64 / S;
   const uint32_t sl = threadIdx.x / PPW;
   const size_t p = (size_t)blockIdx.x * PPW + (threadIdx.x % PPW);
   int32_t st = 0;
-  uint4 r0 = recs[0], r1 = recs[1];
+  uint4 r0 = recs[2 * (size_t)begin], r1 = recs[2 * (size_t)begin + 1];
   // Rows of terms follow each other without gaps from one instruction to the next, so the fetches
   // run ahead of the row in work regardless of where an instruction ends: the term of row r + 3,
   // the wire value and the coefficient of row r + 2.  t0 / x0 / k0 belong to the row in work.
-  const uint2* tp = terms + sl;
+  const uint2* tp = terms + __builtin_amdgcn_readfirstlane(r1.x) + sl;
   uint2 t0 = tp[0], t1 = tp[S], t2 = tp[2 * S];
   Fr x0 = bi_ld(w, t0.x & R1CS_IDX_MASK, p, Bp), x1 = bi_ld(w, t1.x & R1CS_IDX_MASK, p, Bp);
   Fr k0 = coeffs[t0.y & R1CS_IDX_MASK], k1 = coeffs[t1.y & R1CS_IDX_MASK];
-  for (uint32_t i = 0; i < n_instr; i++) {
+  for (uint32_t i = begin; i < end; i++) {
     const uint32_t kind = __builtin_amdgcn_readfirstlane(r0.x);
     const uint32_t target = __builtin_amdgcn_readfirstlane(r0.y);
     const uint32_t mul_rows = __builtin_amdgcn_readfirstlane(r1.y);
     const uint32_t unit_rows = __builtin_amdgcn_readfirstlane(r1.z);
     const uint32_t k = __builtin_amdgcn_readfirstlane(r1.w);
     const Fr kinv = coeffs[__builtin_amdgcn_readfirstlane(r0.w)];
+    const uint32_t par = EXT ? __builtin_amdgcn_readfirstlane(r0.z) : 0u;   // width, operation, size
     Fr sa = Fr::zero(), sb = Fr::zero(), sc = Fr::zero();
     // v joins the sum its tag names; a padding term joins none
     auto accumulate = [&](uint32_t tag, const Fr& v) {
@@ -121,12 +134,54 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
     // the next instruction's record, before this one's stores
     r0 = recs[2 * (size_t)(i + 1)];
     r1 = recs[2 * (size_t)(i + 1) + 1];
-    if (S > 1) {
+    if (S > 1 && !(EXT && kind == RK_COUNT_Q)) {   // a query is its sub-lane's own sum
       sa = sum_sublanes<S>(sa);
       sb = sum_sublanes<S>(sb);
       sc = sum_sublanes<S>(sc);
     }
-    if (kind == RK_NBITS) {
+    if (EXT && kind >= RK_LIMBS) {
+      if (kind == RK_BYTEOP) {
+        const uint32_t u = from_mont(sa).v[0], v = from_mont(sb).v[0];
+        const Fr xs = r1cs_small(par == 1 ? u ^ v : u & v);
+        if (sl == 0) bi_st(w, target, p, Bp, xs);
+        if ((t0.x & R1CS_IDX_MASK) == target) x0 = xs;
+        if ((t1.x & R1CS_IDX_MASK) == target) x1 = xs;
+      } else if (kind == RK_COUNT_Q) {
+        // k queries, one per sub-lane; a query outside the table (coef = its size) counts nowhere
+        const Fr v = from_mont(sa);
+        if (sl < k && (v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0 &&
+            v.v[0] < par) {
+          uint32_t* cnt = reinterpret_cast<uint32_t*>(reinterpret_cast<uint4*>(w) +
+                                                      (size_t)outs[target + v.v[0]] * 2 * Bp + p);
+          __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      } else if (kind != RK_COMMIT) {   // (a launch ends in front of a commitment)
+        if (kind == RK_LIMBS) {
+          // the sub-lanes split the k output wires
+          const Fr v = from_mont(sa);
+          for (uint32_t j = sl; j < k; j += S)
+            bi_st(w, outs[target + j], p, Bp, r1cs_small(r1cs_limb(v, j * par, par)));
+        } else if (kind == RK_COUNT_BEGIN) {
+          // the sub-lanes zero the k counters; the stores are complete before the first count
+          for (uint32_t j = sl; j < k; j += S) bi_st(w, outs[target + j], p, Bp, Fr::zero());
+          __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+        } else {   // RK_COUNT_END: the counts are complete; integers into field images, in place
+          __builtin_amdgcn_s_waitcnt(0x0F70);
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+          for (uint32_t j = sl; j < k; j += S) {
+            const uint32_t wire = outs[target + j];
+            uint32_t* cnt = reinterpret_cast<uint32_t*>(reinterpret_cast<uint4*>(w) + (size_t)wire * 2 * Bp + p);
+            bi_st(w, wire, p, Bp,
+                  r1cs_small(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+          }
+        }
+        // the wire values fetched ahead may be among the wires stored: fetch them again behind the stores
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        x0 = bi_ld(w, t0.x & R1CS_IDX_MASK, p, Bp);
+        x1 = bi_ld(w, t1.x & R1CS_IDX_MASK, p, Bp);
+      }
+    } else if (kind == RK_NBITS) {
       // the sub-lanes split the k output wires
       const Fr v = from_mont(sa);
       for (uint32_t j = sl; j < k; j += S) {
@@ -192,17 +247,28 @@ __global__ void r1cs_solve_init_kernel(Fr* w, int32_t* status, size_t Bp) {
 
 template <int S>
 static void launch_r1cs_solve(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, Fr* w, Fr* a, Fr* b, Fr* c,
-                              int32_t* status, size_t Bp) {
-  hipLaunchKernelGGL(r1cs_solve_kernel<S>, dim3((unsigned)(Bp * S / 64)), dim3(64), 0, ctx->stream,
-                     s->records, s->terms, s->coeffs, s->outs, w, a, b, c, status, Bp, s->n_instr);
+                              int32_t* status, size_t Bp, uint32_t begin, uint32_t end) {
+  const auto kernel = s->ext ? r1cs_solve_kernel<S, true> : r1cs_solve_kernel<S, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(Bp * S / 64)), dim3(64), 0, ctx->stream, s->records,
+                     s->terms, s->coeffs, s->outs, w, a, b, c, status, Bp, begin, end);
 }
 
-// w [n_wires][Bp] with rows 1 .. n_inputs filled: writes every other wire row, a / b / c rows
-// [0, n_constraints) and status[Bp], all in gnark's image
-static int r1cs_solve_bi(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, Fr* w, Fr* a, Fr* b, Fr* c,
-                         int32_t* status, size_t Bp) {
+// ONE and a clean status into w [n_wires][Bp] / status[Bp], in front of the first r1cs_solve_range
+static int r1cs_solve_init(zkmi_ctx* ctx, Fr* w, int32_t* status, size_t Bp) {
   hipLaunchKernelGGL(r1cs_solve_init_kernel, dim3((unsigned)(Bp / 64)), dim3(64), 0, ctx->stream, w,
                      status, Bp);
+  ZK_HIP(hipGetLastError());
+  return ZKMI_OK;
+}
+
+// the records [begin, end) of the plan, begin <= end <= n_records
+static int r1cs_solve_range(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, Fr* w, Fr* a, Fr* b, Fr* c,
+                            int32_t* status, size_t Bp, uint32_t begin, uint32_t end) {
+  if (begin > end || end > s->n_records) {
+    ctx->err = "r1cs solver: record range outside the plan";
+    return ZKMI_ERR_ARG;
+  }
+  if (begin == end) return ZKMI_OK;
   decltype(&launch_r1cs_solve<1>) launch;
   switch (s->S) {
     case 1: launch = launch_r1cs_solve<1>; break;
@@ -216,9 +282,17 @@ static int r1cs_solve_bi(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, Fr* w, Fr* a,
       ctx->err = "r1cs solver: lanes_per_proof must be a power of two, 1 .. 64";
       return ZKMI_ERR_ARG;
   }
-  launch(ctx, s, w, a, b, c, status, Bp);
+  launch(ctx, s, w, a, b, c, status, Bp, begin, end);
   ZK_HIP(hipGetLastError());
   return ZKMI_OK;
+}
+
+// w [n_wires][Bp] with rows 1 .. n_inputs filled: writes every other wire row, a / b / c rows
+// [0, n_constraints) and status[Bp], all in gnark's image
+static int r1cs_solve_bi(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, Fr* w, Fr* a, Fr* b, Fr* c,
+                         int32_t* status, size_t Bp) {
+  int rc = r1cs_solve_init(ctx, w, status, Bp);
+  return rc ? rc : r1cs_solve_range(ctx, s, w, a, b, c, status, Bp, 0, s->n_records);
 }
 
 // n elements of a caller array (host or device) into a host vector
@@ -309,6 +383,9 @@ static int solver_load(zkmi_ctx* ctx, const zkmi_r1cs* m, const zkmi_r1cs_solver
   s->n_constraints = m->n_constraints;
   s->n_inputs = d->n_public - 1 + d->n_secret;
   s->n_instr = plan.n_instr;
+  s->n_records = (uint32_t)plan.records.size() - 1;
+  s->ext = plan.ext;
+  s->commits = std::move(plan.commits);
   s->S = plan.S;
   s->longest = plan.longest;
   s->n_inversions = plan.n_inversions;
@@ -383,6 +460,11 @@ int zkmi_r1cs_solve_batch(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, const void* 
     ctx->err = "r1cs_solve_batch: null argument";
     return ZKMI_ERR_ARG;
   }
+  if (!s->commits.empty()) {
+    ctx->err = "r1cs_solve_batch: this solver holds commitment hints, whose values need a proving key: "
+               "use zkmi_prove_r1cs_submit";
+    return ZKMI_ERR_ARG;
+  }
   const size_t Bp = round_up(batch, 64), nc = s->n_constraints;
   Staged si(ctx), sw(ctx), sabc(ctx), sst(ctx);
   if ((rc = si.in(inputs, batch * (size_t)s->n_inputs * 32))) return rc;
@@ -421,10 +503,27 @@ int zkmi_prove_r1cs_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_sol
     return ZKMI_ERR_ARG;
   }
   // checked before anything is queued: a refused call leaves no batch in flight
-  if (!pk->commits.empty()) {
-    ctx->err = "prove_r1cs_submit: this key has commitments; the commitment hint is not supported on "
-               "this entry: solve with gnark and use zkmi_prove_witness_submit";
+  if (!pk->commits.empty() && s->commits.empty()) {
+    ctx->err = "prove_r1cs_submit: this key has commitments; the solver holds no commitment hint: load "
+               "it with ZKMI_HINTS_STD, or solve with gnark and use zkmi_prove_witness_submit";
     return ZKMI_ERR_ARG;
+  }
+  if (s->commits.size() != pk->commits.size()) {
+    ctx->err = "prove_r1cs_submit: the solver holds " + std::to_string(s->commits.size()) +
+               " commitment hints, the proving key " + std::to_string(pk->commits.size()) + " commitments";
+    return ZKMI_ERR_ARG;
+  }
+  for (size_t i = 0; i < s->commits.size(); i++) {
+    const R1csCommit& sc = s->commits[i];
+    const zkmi_commit_key& ck = pk->commits[i];
+    const char* what = sc.wire != ck.wire ? "lands on different wires" :
+                       sc.hashed != ck.hashed ? "hashes different wires" :
+                       sc.priv != ck.priv ? "commits to different private wires" : nullptr;
+    if (what) {
+      ctx->err = "prove_r1cs_submit: commitment " + std::to_string(i) + " (instruction " +
+                 std::to_string(sc.instr) + ") " + what + " in the solver and in the proving key";
+      return ZKMI_ERR_ARG;
+    }
   }
   if (pk->n_wires != s->n_wires) {
     ctx->err = "prove_r1cs_submit: proving key and solver disagree on the number of wires";
@@ -447,7 +546,19 @@ int zkmi_prove_r1cs_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_sol
   const void* in_dev;
   rc = device_view(ctx, inputs, batch * (size_t)s->n_inputs * 32, stage, &in_dev);
   if (!rc) rc = transpose_in(ctx, in_dev, w + Bp, s->n_inputs, batch, Bp, 32);
-  if (!rc) rc = r1cs_solve_bi(ctx, s, w, (Fr*)S.a.p, (Fr*)S.b.p, (Fr*)S.c.p, (int32_t*)S.st, Bp);
+  // as zkmi_prove_submit: the solve stops at every commitment hint; the commitment is an MSM over
+  // the wires solved so far, its hash becomes the commitment wire's value (commit.hip)
+  Fr *a = (Fr*)S.a.p, *b = (Fr*)S.b.p, *c = (Fr*)S.c.p;
+  int32_t* st = (int32_t*)S.st;
+  if (!rc) rc = r1cs_solve_init(ctx, w, st, Bp);
+  uint32_t begin = 0;
+  for (size_t i = 0; !rc && i < s->commits.size(); i++) {
+    rc = r1cs_solve_range(ctx, s, w, a, b, c, st, Bp, begin, s->commits[i].record);
+    if (!rc) rc = commit_phase(ctx, S, (uint32_t)i, true);
+    begin = s->commits[i].record + 1;
+  }
+  if (!rc) rc = r1cs_solve_range(ctx, s, w, a, b, c, st, Bp, begin, s->n_records);
+  if (!rc && !s->commits.empty()) rc = commit_finish_submit(ctx, S);
   return prove_set_end(ctx, main, rc);
 }
 

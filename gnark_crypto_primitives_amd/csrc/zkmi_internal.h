@@ -168,6 +168,7 @@ struct zkmi_msm_bases {
 struct zkmi_commit_key {
   uint32_t n_private = 0, n_hashed = 0, wire = 0;
   std::vector<uint32_t> hashed;     // host copy (rows read back for the hash)
+  std::vector<uint32_t> priv;       // host copy (zkmi_prove_r1cs_submit compares it with the solver's)
   uint32_t* private_dev = nullptr;  // device: wire index of every basis point
   zkmi_msm_bases* basis = nullptr;  // side tables
   zkmi_msm_bases* sigma = nullptr;  // main-stream tables (proof of knowledge)

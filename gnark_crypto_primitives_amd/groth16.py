@@ -288,14 +288,19 @@ class Prover:
         self.r1cs_h = self.ctx.r1cs_load(rd)
         return self.r1cs_h
 
-    def load_r1cs_solver(self, lanes_per_proof=0):
+    def load_r1cs_solver(self, lanes_per_proof=0, hints="basic"):
         """zkmi_r1cs_solver_load: the GPU solver of the gnark-shaped system, described the way a
         gnark ccs describes it -- L, R, O, the instruction order and the hint table.  The frontend's
         solve wires and its witness program are deliberately left out: the library finds every
-        constraint's unknown itself.  lanes_per_proof: 0 = auto, or a power of two, 1 .. 64; a
-        solver loaded with another value is replaced."""
+        constraint's unknown itself.  lanes_per_proof: 0 = auto, or a power of two, 1 .. 64.
+        hints: "basic" (InvZero, NBits) or "std" (additionally limbs, lookup multiplicities, byte
+        operations and commitments: ZKMI_HINTS_STD).  A solver loaded with other arguments is
+        replaced."""
+        sets = {"basic": _lib.HINTS_BASIC, "std": _lib.HINTS_STD}
+        if hints not in sets:
+            raise ValueError('hints must be "basic" or "std"')
         if getattr(self, "r1cs_solver_h", None):
-            if lanes_per_proof == self._r1cs_solver_lanes:
+            if (lanes_per_proof, hints) == self._r1cs_solver_args:
                 return self.r1cs_solver_h
             self.ctx.r1cs_solver_free(self.r1cs_solver_h)
             self.r1cs_solver_h = None
@@ -304,9 +309,9 @@ class Prover:
         arrs = [np.ascontiguousarray(x, dtype=np.uint32) for x in
                 (cc.instr, kinds, in_ptr, lc_ptr, np.stack([hcid, hcol], axis=1), out_ptr, outs)]
         sd = _lib.R1csSolverDesc(cc.n_public, cc.n_secret, cc.instr.shape[0], len(kinds),
-                                 *[a.ctypes.data for a in arrs], lanes_per_proof)
+                                 *[a.ctypes.data for a in arrs], lanes_per_proof, sets[hints])
         self.r1cs_solver_h = self.ctx.r1cs_solver_load(self.load_r1cs(), sd)
-        self._r1cs_solver_lanes = lanes_per_proof
+        self._r1cs_solver_args = (lanes_per_proof, hints)
         return self.r1cs_solver_h
 
     def _r1cs_solver(self):

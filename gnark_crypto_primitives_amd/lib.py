@@ -59,7 +59,10 @@ class R1csSolverDesc(C.Structure):
                 ("n_hints", C.c_uint32), ("instr", C.c_void_p), ("hint_kind", C.c_void_p),
                 ("hint_in_ptr", C.c_void_p), ("hint_lc_ptr", C.c_void_p), ("hint_terms", C.c_void_p),
                 ("hint_out_ptr", C.c_void_p), ("hint_out", C.c_void_p),
-                ("lanes_per_proof", C.c_uint32)]
+                ("lanes_per_proof", C.c_uint32), ("hint_set", C.c_uint32)]
+
+
+HINTS_BASIC, HINTS_STD = 0, 1      # enum zkmi_hint_set
 
 
 # every symbol include/zkmi.h declares: (name, restype, argtypes)

@@ -332,10 +332,27 @@ int zkmi_prove_witness_batch(zkmi_ctx* ctx, const zkmi_pk* pk, const void* wires
  * Hints are named by kind number; a shim maps gnark's hint names to them.  Supported kinds: */
 enum zkmi_hint_kind {
   ZKMI_HINT_INVZERO = 1, /* solver.InvZeroHint: one input x, one output 1/x, or 0 for x = 0 */
-  ZKMI_HINT_NBITS = 2    /* bits.NBits: one input, output i = bit i of its canonical value */
+  ZKMI_HINT_NBITS = 2,   /* bits.NBits: one input, output i = bit i of its canonical value */
+  /* The kinds below are accepted under hint_set = ZKMI_HINTS_STD only.  Their first input
+   * expression is a constant parameter p0: terms on wire 0 (ONE) alone, evaluated at load time. */
+  ZKMI_HINT_LIMBS = 3,   /* p0 = width (1 .. 64), one value expression; output j = bits
+                            [j width, (j + 1) width) of its canonical value, bits from 256 on are 0 */
+  ZKMI_HINT_COUNT = 4,   /* p0 = table size = number of outputs; every further input is a query;
+                            output j = number of queries whose canonical value is j (a query >= size
+                            counts nowhere) */
+  ZKMI_HINT_COMMIT = 5,  /* p0 = n_hashed, then the n_hashed hashed operands, then the private ones,
+                            one output: the commitment wire.  Every operand is one solved wire with
+                            coefficient 1.  A phase boundary of zkmi_prove_r1cs_submit, which needs the
+                            key's commitment keys; refused by zkmi_r1cs_solve_batch */
+  ZKMI_HINT_BYTEOP = 6   /* p0 = 1 XOR | 2 AND, two expressions, one output: the operation on the low
+                            32 bits of their canonical values */
 };
-/* Every other kind (3 limbs, 4 lookup multiplicities, 5 commitment, 6 byte operations, 7 emulated
- * product: the numbers of this repository's frontend) is refused by name at load time. */
+/* The numbers are those of this repository's frontend.  Kind 7 (emulated product) and unknown kinds
+ * are refused by name at load time under either hint set. */
+enum zkmi_hint_set {
+  ZKMI_HINTS_BASIC = 0, /* InvZero and NBits; every other kind is refused by name at load time */
+  ZKMI_HINTS_STD = 1    /* additionally limbs, lookup multiplicities, commitment, byte operations */
+};
 typedef struct {
   uint32_t n_public;  /* public wires including ONE */
   uint32_t n_secret;
@@ -351,13 +368,17 @@ typedef struct {
   uint32_t lanes_per_proof;     /* lanes of a wavefront that share one proof's terms: a power of two,
                                    1 .. 64; 0 = the power of two in 1 .. 16 nearest to the mean number
                                    of terms per instruction */
+  uint32_t hint_set;            /* enum zkmi_hint_set; 0 = ZKMI_HINTS_BASIC.  The last field: it takes
+                                   the place of what was tail padding behind lanes_per_proof, so
+                                   sizeof and every other offset are those of a struct without it, and
+                                   a caller that zero-initialises the struct gets the basic set */
 } zkmi_r1cs_solver_desc;
 typedef struct zkmi_r1cs_solver zkmi_r1cs_solver;
 /* Builds the solve plan on the host (csrc/r1cs_plan.h) and uploads it; `r1cs` and the host arrays
  * may be freed afterwards.  ZKMI_ERR_ARG with a message that names the instruction when a
  * constraint has two unknown wires, its unknown occurs twice, a hint reads an unsolved wire, an
- * index is out of range, a constraint occurs twice or never, a wire stays unsolved, or a hint is of
- * an unsupported kind. */
+ * index is out of range, a constraint occurs twice or never, a wire stays unsolved, a hint is of
+ * a kind outside desc->hint_set, or a hint's operands, outputs or parameter do not fit its kind. */
 int zkmi_r1cs_solver_load(zkmi_ctx* ctx, const zkmi_r1cs* r1cs, const zkmi_r1cs_solver_desc* desc,
                           zkmi_r1cs_solver** out);
 void zkmi_r1cs_solver_free(zkmi_ctx* ctx, zkmi_r1cs_solver* solver);
@@ -367,12 +388,17 @@ void zkmi_r1cs_solver_free(zkmi_ctx* ctx, zkmi_r1cs_solver* solver);
 int zkmi_r1cs_solver_info(const zkmi_r1cs_solver* solver, uint64_t* info /* 8 */);
 /* Witness solve only, the conventions of zkmi_solve_batch: inputs batch x (n_public - 1 + n_secret),
  * wires_out (optional) batch x n_wires, abc_out (optional) 3 x batch x n_constraints, status_out per
- * proof 0 or ZKMI_ERR_UNSATISFIED (an assertion fails, or the factor a solve divides by is 0). */
+ * proof 0 or ZKMI_ERR_UNSATISFIED (an assertion fails, or the factor a solve divides by is 0).
+ * A solver whose plan holds commitment hints is refused: their values need a proving key
+ * (zkmi_prove_r1cs_submit). */
 int zkmi_r1cs_solve_batch(zkmi_ctx* ctx, const zkmi_r1cs_solver* solver, const void* inputs,
                           size_t batch, void* wires_out, void* abc_out, int32_t* status_out);
 /* Stage 1 of a prove from inputs; the matching zkmi_prove_collect returns the proofs.  Pipelines
- * exactly like zkmi_prove_submit (two batches in flight, same streams, same HBM plan).  Keys with
- * commitments are refused before anything is queued. */
+ * exactly like zkmi_prove_submit (two batches in flight, same streams, same HBM plan).  A key with
+ * commitments needs a solver loaded with ZKMI_HINTS_STD whose commitment hints match the key's
+ * commitments one by one (commitment wire, hashed and private wires, in order): the solve stops at
+ * each, the commitment is formed and hashed into its wire, and zkmi_prove_collect_ex returns
+ * commitments and proof of knowledge.  Every mismatch is refused before anything is queued. */
 int zkmi_prove_r1cs_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_solver* solver,
                            const void* inputs, size_t batch, const void* rs);
 

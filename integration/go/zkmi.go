@@ -23,8 +23,10 @@
 //
 // Without gnark's solver: LoadSolver(ccs) uploads the instruction order and the hint table of the
 // ccs (zkmi_r1cs_solver_load), SubmitInputs ships the public and secret inputs only and the GPU
-// solves (zkmi_prove_r1cs_submit; tests/test_gpu_r1cs_solver.py drives that sequence).  Hints
-// solver.InvZeroHint and bits.NBits only; everything else, and keys with commitments, is refused.
+// solves (zkmi_prove_r1cs_submit; tests/test_gpu_r1cs_solver.py and tests/test_gpu_r1cs_hints.py
+// drive that sequence).  Hints solver.InvZeroHint and bits.NBits; with LoadSolver(..., std = true)
+// also the limb, lookup-multiplicity, byte-operation and commitment hints, so keys with commitments
+// go through it as well.  The emulated-product hint and every other hint is refused.
 package zkmi
 
 /*
@@ -207,18 +209,31 @@ type Solver struct {
 
 // hintKinds maps gnark's hint names to the kind numbers of include/zkmi.h.  The names are what
 // solver.GetHintName returns for solver.InvZeroHint and bits.NBits [UPSTREAM-RECALL: unpinned].
+// The four kinds of ZKMI_HINTS_STD follow: the limb decomposition of std/rangecheck, the lookup
+// multiplicities of std/internal/logderivarg, the byte XOR / AND of std/math/uints and the
+// commitment placeholder of the Groth16 builder [UPSTREAM-RECALL: names and operand order
+// unpinned].  The library's contract for them (include/zkmi.h: a constant parameter first, then the
+// value expressions) is the one of this repository's frontend and of the C oracle; parity of this
+// table and of the operand order with gnark's own hints is not pinned by any test here.
 var hintKinds = map[string]uint32{
-	"github.com/consensys/gnark/constraint/solver.InvZeroHint": C.ZKMI_HINT_INVZERO,
-	"github.com/consensys/gnark/std/math/bits.NBits":           C.ZKMI_HINT_NBITS,
+	"github.com/consensys/gnark/constraint/solver.InvZeroHint":                    C.ZKMI_HINT_INVZERO,
+	"github.com/consensys/gnark/std/math/bits.NBits":                              C.ZKMI_HINT_NBITS,
+	"github.com/consensys/gnark/std/rangecheck.DecomposeHint":                     C.ZKMI_HINT_LIMBS,   // [UPSTREAM-RECALL]
+	"github.com/consensys/gnark/std/internal/logderivarg.countHint":               C.ZKMI_HINT_COUNT,   // [UPSTREAM-RECALL]
+	"github.com/consensys/gnark/frontend/cs/r1cs.bsb22CommitmentComputePlaceholder": C.ZKMI_HINT_COMMIT, // [UPSTREAM-RECALL]
+	"github.com/consensys/gnark/std/math/uints.xorHint":                           C.ZKMI_HINT_BYTEOP,  // [UPSTREAM-RECALL]
+	"github.com/consensys/gnark/std/math/uints.andHint":                           C.ZKMI_HINT_BYTEOP,  // [UPSTREAM-RECALL]
 }
 
 // LoadSolver walks ccs.Instructions in order [UPSTREAM-RECALL: constraint.System{Instructions,
 // Blueprints}, PackedInstruction.Unpack, BlueprintHint.DecompressHint, HintMapping{HintID, Inputs,
 // OutputRange}] and describes them as zkmi_r1cs_solver_desc does: (0, constraint index) for every
 // R1C, in the order GetR1Cs enumerates them, and (1, hint index) with the hint's input expressions
-// and output wires.  A hint that is neither InvZero nor NBits gets kind 0 here, which the library
-// refuses by instruction.  r1cs is the handle of LoadR1CS for the same ccs.
-func (d *Device) LoadSolver(ccs *cs_bn254.R1CS, r1cs *R1CS, lanesPerProof int) (*Solver, error) {
+// and output wires.  A hint that is not in hintKinds gets kind 0 here, which the library refuses by
+// instruction.  std selects ZKMI_HINTS_STD (limbs, lookup multiplicities, byte operations,
+// commitments); without it the description is the basic one and those kinds are refused by name.
+// r1cs is the handle of LoadR1CS for the same ccs.
+func (d *Device) LoadSolver(ccs *cs_bn254.R1CS, r1cs *R1CS, lanesPerProof int, std bool) (*Solver, error) {
 	names := make(map[solver.HintID]string)
 	for id, name := range ccs.MHintsDependencies {
 		names[id] = name
@@ -274,6 +289,9 @@ func (d *Device) LoadSolver(ccs *cs_bn254.R1CS, r1cs *R1CS, lanesPerProof int) (
 		desc.hint_terms = (*C.zkmi_term)(unsafe.Pointer(&terms[0]))
 	}
 	desc.lanes_per_proof = C.uint32_t(lanesPerProof) // 0 = auto
+	if std {
+		desc.hint_set = C.ZKMI_HINTS_STD // calloc left ZKMI_HINTS_BASIC
+	}
 	d.mu.Lock()
 	defer d.mu.Unlock()
 	var h *C.zkmi_r1cs_solver
