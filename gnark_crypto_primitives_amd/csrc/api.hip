@@ -1,5 +1,7 @@
 // C-ABI of libzkmi.so (include/zkmi.h) and the Groth16 prove pipeline that strings the kernels
-// together: solve -> quotient (7 NTTs) -> 4 G1 MSMs + 1 G2 MSM -> assembly.
+// together: solve -> quotient -> 4 G1 MSMs + 1 G2 MSM -> assembly.  The quotient is six transforms
+// (compute_h_bi; gnark's seven below 2^8), or the four that take a and b to the coset when the key
+// was loaded with its quotient bases in evaluation form (compute_ab_coset_bi, quotient_fold.hip).
 // Stands in for groth16.Prove in gnark backend/groth16/bn254/prove.go [UPSTREAM-RECALL,
 // SURVEY.md §3.2].  There is no CPU fallback anywhere in this file.
 #include <algorithm>
@@ -554,6 +556,34 @@ int zkmi_h_batch(zkmi_ctx* ctx, const void* a, const void* b, const void* c, voi
   return ZKMI_OK;
 }
 
+int zkmi_ab_coset_batch(zkmi_ctx* ctx, const void* a, const void* b, void* out, int log_n,
+                        size_t batch) {
+  ZK_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
+  if (batch == 0) return ZKMI_OK;
+  NttPlan* plan;
+  if ((rc = get_plan(ctx, log_n, &plan))) return rc;
+  const size_t n = (size_t)1 << log_n, Bp = round_up(batch, 64);
+  Staged sa(ctx), sb(ctx), so(ctx);
+  if ((rc = sa.in(a, batch * n * 32)) || (rc = sb.in(b, batch * n * 32)) ||
+      (rc = so.out(out, batch * n * 32)))
+    return rc;
+  void* t[3];
+  DevBuf* tb[3] = {&ctx->sets[0].a, &ctx->sets[0].b, &ctx->ntt_tmp};
+  for (int i = 0; i < 3; i++)
+    if ((rc = ensure_scratch(ctx, *tb[i], n * Bp * 32, &t[i]))) return rc;
+  if ((rc = transpose_in(ctx, sa.dev, t[0], n, batch, Bp, 32)) ||
+      (rc = transpose_in(ctx, sb.dev, t[1], n, batch, Bp, 32)))
+    return rc;
+  Fr* u;
+  if ((rc = compute_ab_coset_bi(ctx, plan, (Fr*)t[0], (Fr*)t[1], (Fr*)t[2], Bp, n, &u))) return rc;
+  if ((rc = transpose_out(ctx, u, so.dev, n, batch, Bp, 32))) return rc;
+  if ((rc = so.finish())) return rc;
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  return ZKMI_OK;
+}
+
 // window_bits: 0 = as many bits per window as the table budget allows (windows of mixed width
 // summing to exactly 255 bits); 2..16 = uniform windows of that width.  If the table cannot be
 // allocated the plan is relaxed (more, narrower windows) until it fits.
@@ -859,13 +889,25 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
     ctx->err = "pk: msm_chunk_factor must be in [0,64]";
     return ZKMI_ERR_ARG;
   }
+  // Quotient in evaluation form: E in the place of Z (n bases), the c term folded into the K bases
+  // (quotient_fold.h).  The results wait on the host and every device buffer of the fold is freed
+  // again, so the tables below are planned against the same free HBM as those of an unfolded key.
+  FoldedKey fold;
+  if (d->fold_r1cs) {
+    const int frc = quotient_fold_key(ctx, d, wk, &fold);
+    if (frc) return frc;
+  }
+  const uint32_t n_kb = fold.folded ? (uint32_t)fold.k_wire.size() : d->n_k;
+  const uint32_t n_zb = fold.folded ? n_z + 1 : n_z;
   auto* pk = new zkmi_pk();
   pk->log_n = d->log_n;
   pk->n_wires = d->n_wires;
   pk->n_a = d->n_a;
   pk->n_b = d->n_b;
-  pk->n_k = d->n_k;
-  pk->n_z = n_z;
+  pk->n_k = n_kb;
+  pk->n_z = n_zb;
+  pk->folded = fold.folded;
+  pk->fold_n_constraints = fold.folded ? d->fold_r1cs->n_constraints : 0;
   pk->max_batch = d->max_batch ? d->max_batch : 1024;
   int rc;
   // commitment keys first (per-window tables of the Pedersen bases, 2 x 33 KB per committed wire at
@@ -877,9 +919,9 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
   // One window plan per group for the whole key.  Auto plans are sized against the free HBM minus
   // the working set of the largest batch the caller will prove (and the caller's own cap).
   const bool auto1 = d->window_bits_g1 == 0, auto2 = d->window_bits_g2 == 0;
-  const size_t n1 = (size_t)d->n_a + d->n_b + d->n_k + n_z;
+  const size_t n1 = (size_t)d->n_a + d->n_b + n_kb + n_zb;
   const size_t n_msm_max = std::max(std::max((size_t)d->n_a, (size_t)d->n_b),
-                                    std::max((size_t)d->n_k, (size_t)n_z));
+                                    std::max((size_t)n_kb, (size_t)n_zb));
   const size_t n_slots = d->n_slots_hint ? d->n_slots_hint : (size_t)d->n_wires + d->n_wires / 20;
   const double ws = prove_working_set_bytes(d->log_n, n_slots, d->n_wires, pk->max_batch, n_msm_max,
                                             pk->commits.size());
@@ -911,16 +953,16 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
   // group (window 0) whatever the group size, so they get small subset-sum tables and the dense
   // quotient MSM (h . Z) gets the HBM: the widest table that fits, sign patterns allowed.
   WinPlan p1z = p1;
-  if (d->sparse_witness >= 2 && auto1 && auto2 && n1 >= 4096 && n_z >= 4096) {
+  if (d->sparse_witness >= 2 && auto1 && auto2 && n1 >= 4096 && n_zb >= 4096) {
     const int kw = 12;
     const double wire_bytes =
-        (double)((d->n_a + kw - 1) / kw + (d->n_b + kw - 1) / kw + (d->n_k + kw - 1) / kw) *
+        (double)((d->n_a + kw - 1) / kw + (d->n_b + kw - 1) / kw + (n_kb + kw - 1) / kw) *
             (double)(1u << kw) * 64.0 +
         (double)((d->n_b + kw - 1) / kw) * (double)(1u << kw) * 128.0;
     if (wire_bytes < 0.5 * usable) {
       int kz = 0, k2 = 0;
       bool sz = true, s2 = true;
-      plan_comb_for_budget(n_z, 0, 0.98 * usable - wire_bytes, &kz, &k2, &sz, &s2, true);
+      plan_comb_for_budget(n_zb, 0, 0.98 * usable - wire_bytes, &kz, &k2, &sz, &s2, true);
       p1 = plan_comb(kw, false);
       p2 = plan_comb(kw, false);
       p1z = plan_comb(kz, sz);
@@ -937,11 +979,11 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
   };
   if ((rc = upload_u32(ctx, wa.data(), d->n_a, &pk->a_wire)) ||
       (rc = upload_u32(ctx, wb.data(), d->n_b, &pk->b_wire)) ||
-      (rc = upload_u32(ctx, wk.data(), d->n_k, &pk->k_wire)) ||
+      (rc = upload_u32(ctx, fold.folded ? fold.k_wire.data() : wk.data(), n_kb, &pk->k_wire)) ||
       (rc = load(1, d->g1_a, d->n_a, p1, auto1, &pk->A)) ||
       (rc = load(1, d->g1_b, d->n_b, p1, auto1, &pk->B1)) ||
-      (rc = load(1, d->g1_k, d->n_k, p1, auto1, &pk->K)) ||
-      (rc = load(1, d->g1_z, n_z, p1z, auto1, &pk->Z)) ||
+      (rc = load(1, fold.folded ? (const void*)fold.k.data() : d->g1_k, n_kb, p1, auto1, &pk->K)) ||
+      (rc = load(1, fold.folded ? (const void*)fold.e.data() : d->g1_z, n_zb, p1z, auto1, &pk->Z)) ||
       (rc = load(2, d->g2_b, d->n_b, p2, auto2, &pk->B2))) {
     zkmi_pk_free(ctx, pk);
     return rc;
@@ -979,6 +1021,8 @@ int zkmi_pk_info(const zkmi_pk* pk, uint64_t* info) {
   info[9] = pk->B2->plan.comb;
   return ZKMI_OK;
 }
+
+int zkmi_pk_folded(const zkmi_pk* pk) { return pk && pk->folded ? 1 : 0; }
 
 void zkmi_cs_free(zkmi_ctx* ctx, zkmi_cs* cs) {
   if (!cs) return;
@@ -1112,6 +1156,12 @@ int zkmi_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_cs* cs, const
     ctx->err = "prove: domain smaller than the number of constraints";
     return ZKMI_ERR_ARG;
   }
+  if (pk->folded && cs->n_constraints != pk->fold_n_constraints) {
+    ctx->err = "prove: the key was folded (zkmi_pk_desc.fold_r1cs) with a system of " +
+               std::to_string(pk->fold_n_constraints) + " constraints, this one has " +
+               std::to_string(cs->n_constraints);
+    return ZKMI_ERR_ARG;
+  }
   if (cs->commit_rows.size() != pk->commits.size()) {
     ctx->err = "prove: the constraint system has " + std::to_string(cs->commit_rows.size()) +
                " commitments, the proving key " + std::to_string(pk->commits.size());
@@ -1178,9 +1228,12 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
   Fr* slots = (Fr*)S.slots.p;
   ZK_HIP(hipStreamWaitEvent(ctx->stream, S.ev1, 0));
   hipEventRecord(S.evq[0], ctx->stream);
+  // h: the quotient's coefficients, or (folded key) the coset evaluations of a b; S.c is not read
   Fr* h;
-  if ((rc = compute_h_bi(ctx, plan, (Fr*)S.a.p, (Fr*)S.b.p, (Fr*)S.c.p, (Fr*)t0, Bp,
-                         S.n_constraints, &h, fd)))
+  if ((rc = pk->folded ? compute_ab_coset_bi(ctx, plan, (Fr*)S.a.p, (Fr*)S.b.p, (Fr*)t0, Bp,
+                                             S.n_constraints, &h, fd)
+                       : compute_h_bi(ctx, plan, (Fr*)S.a.p, (Fr*)S.b.p, (Fr*)S.c.p, (Fr*)t0, Bp,
+                                      S.n_constraints, &h, fd)))
     return rc;
   hipEventRecord(S.evq[1], ctx->stream);
   S.msm_ev_used = 0;

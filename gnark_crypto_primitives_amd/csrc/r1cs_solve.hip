@@ -533,6 +533,12 @@ int zkmi_prove_r1cs_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_sol
     ctx->err = "prove_r1cs_submit: domain smaller than the number of constraints";
     return ZKMI_ERR_ARG;
   }
+  if (pk->folded && s->n_constraints != pk->fold_n_constraints) {
+    ctx->err = "prove_r1cs_submit: the key was folded (zkmi_pk_desc.fold_r1cs) with a system of " +
+               std::to_string(pk->fold_n_constraints) + " constraints, this one has " +
+               std::to_string(s->n_constraints);
+    return ZKMI_ERR_ARG;
+  }
   hipStream_t main;
   char* stage;
   int rc = prove_set_begin(ctx, pk, s->n_wires, s->n_inputs, batch, rs, &main, &stage);

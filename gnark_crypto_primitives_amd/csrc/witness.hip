@@ -391,6 +391,12 @@ int zkmi_prove_witness_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs*
     ctx->err = "prove_witness_submit: n_constraints must be in [1, 2^log_n]";
     return ZKMI_ERR_ARG;
   }
+  if (pk->folded && n_constraints != pk->fold_n_constraints) {
+    ctx->err = "prove_witness_submit: the key was folded (zkmi_pk_desc.fold_r1cs) with a system of " +
+               std::to_string(pk->fold_n_constraints) + " constraints, this one has " +
+               std::to_string(n_constraints);
+    return ZKMI_ERR_ARG;
+  }
   // the value file is the wire matrix here; no inputs are staged through misc besides r/s
   hipStream_t main;
   int rc = prove_set_begin(ctx, pk, pk->n_wires, 0, batch, rs, &main, nullptr);

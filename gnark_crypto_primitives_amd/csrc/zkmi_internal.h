@@ -183,6 +183,10 @@ struct zkmi_pk {
   zk::G1Affine alpha, beta1, delta1;
   zk::G2Affine beta2, delta2;
   std::vector<zkmi_commit_key> commits;   // commitment extension (empty for a plain key)
+  // quotient in evaluation form (quotient_fold.h): Z holds E (n bases, n_z = n), K the bases with
+  // the c term folded in (n_k counts the appended ones); the prover runs compute_ab_coset_bi
+  bool folded = false;
+  uint32_t fold_n_constraints = 0;   // rows of the O that was folded in
 };
 
 struct zkmi_cs {
@@ -332,6 +336,26 @@ int ntt_bi(zkmi_ctx* ctx, const NttPlan* plan, const Fr* src, Fr* dst, size_t Bp
 // abc_f: a, b, c are in the F domain (solver output); the result h is always in gnark's image
 int compute_h_bi(zkmi_ctx* ctx, const NttPlan* plan, Fr* a, Fr* b, Fr* c, Fr* t0, size_t Bp,
                  size_t n_valid, Fr** h_out, bool abc_f = false);
+
+// the quotient of a folded key: the n coset evaluations of a * b in gnark's image, *u_out = b
+// (log_n >= 8; a, b as compute_h_bi's, both overwritten)
+int compute_ab_coset_bi(zkmi_ctx* ctx, const NttPlan* plan, Fr* a, Fr* b, Fr* t0, size_t Bp,
+                        size_t n_valid, Fr** u_out, bool abc_f = false);
+
+// quotient_fold.hip: what zkmi_pk_load puts in the place of g1_z, g1_k and k_wire when
+// zkmi_pk_desc.fold_r1cs folds (host copies; the device buffers of the fold are gone on return)
+struct FoldedKey {
+  bool folded = false;
+  std::vector<G1Affine> e, k;
+  std::vector<uint32_t> k_wire;
+};
+// k_wire: the key's K wires on the host.  ZKMI_ERR_ARG for a malformed fold_r1cs; folded stays
+// false, with ZKMI_OK, for a system or a key that the fold does not serve
+int quotient_fold_key(zkmi_ctx* ctx, const zkmi_pk_desc* d, const std::vector<uint32_t>& k_wire,
+                      FoldedKey* out);
+// pts[0, n) = E, pts[n, 2n) = L from the first min(n_z, n - 1) points of z_dev (device arrays)
+int quotient_bases_dev(zkmi_ctx* ctx, const NttPlan* plan, const G1Affine* z_dev, uint32_t n_z,
+                       G1Affine* pts);
 
 // msm.hip (the templates behind these are in msm_impl.h)
 constexpr int COMB_W = 254;   // one-bit windows of a comb plan: scalars are below 2^254

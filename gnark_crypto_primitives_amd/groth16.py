@@ -218,12 +218,15 @@ class Prover:
     def __init__(self, ctx: _lib.Context, cc: CompiledCircuit, pk: ProvingKey,
                  window_bits_g1: int = 0, window_bits_g2: int = 0, *, max_batch: int = 0,
                  table_budget_bytes: int = 0, msm_chunk_factor: int = 0,
-                 gnark_key_layout: bool = False, sparse_witness=None):
+                 gnark_key_layout: bool = False, sparse_witness=None, fold_quotient=None):
         """max_batch / table_budget_bytes / msm_chunk_factor: zkmi_pk_desc plan fields
         (0 = default).  sparse_witness: zkmi_pk_desc.sparse_witness; None = from the circuit (more
         than half of its wires are known booleans: Keccak, bit decompositions).  gnark_key_layout: describe the key the way
         gnark's ProvingKey does (InfinityA / InfinityB byte maps + nbPublic) instead of wire-index
-        arrays; the loaded key is the same."""
+        arrays; the loaded key is the same.  fold_quotient: hand the circuit's O matrix to the key
+        load (zkmi_pk_desc.fold_r1cs) so that the quotient MSM takes evaluations; None = when the
+        key has no commitments.  The library leaves keys with commitments and domains below 2^8
+        unfolded either way (``folded`` tells)."""
         self.ctx, self.cc, self.pk = ctx, cc, pk
         self.n_inputs = cc.n_inputs
         self._consts = to_mont_array(cc.consts) if cc.consts else np.zeros((0, 4), np.uint64)
@@ -258,6 +261,12 @@ class Prover:
         self._keep.append(cdescs)
         if len(getattr(cc, "commitments", [])) != self.n_commitments:
             raise ValueError("circuit and proving key disagree on the number of commitments")
+        fold = None
+        if fold_quotient is None:
+            fold_quotient = not self.n_commitments
+        if fold_quotient and cc.consts and cc.n_constraints:
+            fold, fold_keep = self._r1cs_desc()
+            self._keep += fold_keep + [fold]
         pd = _lib.PkDesc(pk.log_n, pk.n_wires, len(pk.a_wire), len(pk.b_wire), len(pk.k_wire),
                          pk.g1_z.shape[0], *ptrs, window_bits_g1, window_bits_g2,
                          inf_a.ctypes.data if inf_a is not None else None,
@@ -267,14 +276,13 @@ class Prover:
                           int(cc.n_boolean_wires * 2 > cc.n_wires)) if sparse_witness is None
                          else int(sparse_witness),
                          self.n_commitments,
-                         C.addressof(cdescs) if self.n_commitments else None)
+                         C.addressof(cdescs) if self.n_commitments else None,
+                         C.addressof(fold) if fold is not None else None)
         self.pk_h = ctx.pk_load(pd)
+        self.folded = ctx.pk_folded(self.pk_h)
 
-    def load_r1cs(self):
-        """zkmi_r1cs_load of the circuit's L, R, O (gnark: constraint.R1CS terms {CID, VID} and
-        cs.Coefficients): afterwards ``submit_witness`` ships wire vectors only."""
-        if getattr(self, "r1cs_h", None):
-            return self.r1cs_h
+    def _r1cs_desc(self):
+        """(zkmi_r1cs_desc of the circuit's L, R, O and cs.Coefficients, the arrays it points into)"""
         cc = self.cc
         coeffs = to_mont_array(cc.consts)
         keep = [coeffs]
@@ -284,7 +292,15 @@ class Prover:
             ptr = np.ascontiguousarray(ptr, dtype=np.uint32)
             keep += [ptr, terms]
             fields += [ptr.ctypes.data, terms.ctypes.data]
-        rd = _lib.R1csDesc(cc.n_wires, cc.n_constraints, len(cc.consts), coeffs.ctypes.data, *fields)
+        return (_lib.R1csDesc(cc.n_wires, cc.n_constraints, len(cc.consts), coeffs.ctypes.data,
+                              *fields), keep)
+
+    def load_r1cs(self):
+        """zkmi_r1cs_load of the circuit's L, R, O (gnark: constraint.R1CS terms {CID, VID} and
+        cs.Coefficients): afterwards ``submit_witness`` ships wire vectors only."""
+        if getattr(self, "r1cs_h", None):
+            return self.r1cs_h
+        rd, _keep = self._r1cs_desc()
         self.r1cs_h = self.ctx.r1cs_load(rd)
         return self.r1cs_h
 

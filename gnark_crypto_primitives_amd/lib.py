@@ -30,7 +30,7 @@ class PkDesc(C.Structure):
                 ("max_batch", C.c_uint32), ("table_budget_bytes", C.c_uint64),
                 ("n_slots_hint", C.c_uint32), ("msm_chunk_factor", C.c_uint32),
                 ("sparse_witness", C.c_uint32), ("n_commitments", C.c_uint32),
-                ("commitments", C.c_void_p)]
+                ("commitments", C.c_void_p), ("fold_r1cs", C.c_void_p)]
 
 
 class CommitmentDesc(C.Structure):
@@ -78,6 +78,8 @@ SYMBOLS = [
     ("zkmi_field_mul_bench", _I, [_P, _I, _SZ, _I, C.POINTER(C.c_double)]),
     ("zkmi_ntt_batch", _I, [_P, _P, _I, _SZ, _I, _I]),
     ("zkmi_h_batch", _I, [_P, _P, _P, _P, _P, _I, _SZ]),
+    ("zkmi_ab_coset_batch", _I, [_P, _P, _P, _P, _I, _SZ]),
+    ("zkmi_quotient_bases", _I, [_P, _P, _SZ, _I, _P, _P]),
     ("zkmi_msm_bases_load", _I, [_P, _I, _P, _SZ, _I, C.POINTER(_P)]),
     ("zkmi_msm_bases_free", None, [_P, _P]),
     ("zkmi_msm_batch", _I, [_P, _P, _P, _SZ, _P]),
@@ -86,6 +88,7 @@ SYMBOLS = [
     ("zkmi_pk_load", _I, [_P, C.POINTER(PkDesc), C.POINTER(_P)]),
     ("zkmi_pk_free", None, [_P, _P]),
     ("zkmi_pk_info", _I, [_P, C.POINTER(C.c_uint64)]),
+    ("zkmi_pk_folded", _I, [_P]),
     ("zkmi_cs_load", _I, [_P, C.POINTER(CsDesc), C.POINTER(_P)]),
     ("zkmi_cs_free", None, [_P, _P]),
     ("zkmi_solve_batch", _I, [_P, _P, _P, _SZ, _P, _P, _P]),
@@ -220,6 +223,19 @@ class Context:
                                           batch), "zkmi_h_batch")
         return out
 
+    def ab_coset_batch(self, a, b, out, log_n, batch):
+        self._check(self.lib.zkmi_ab_coset_batch(self.h, _ptr(a), _ptr(b), _ptr(out), log_n, batch),
+                    "zkmi_ab_coset_batch")
+        return out
+
+    def quotient_bases(self, g1_z, log_n):
+        """(E, L): uint64 [2^log_n, 8] each, from g1_z [n_z >= 2^log_n - 1, 8] (zkmi_quotient_bases)"""
+        n = 1 << log_n
+        e, l = np.zeros((n, 8), dtype=np.uint64), np.zeros((n, 8), dtype=np.uint64)
+        self._check(self.lib.zkmi_quotient_bases(self.h, _ptr(g1_z), g1_z.shape[0], log_n, _ptr(e),
+                                                 _ptr(l)), "zkmi_quotient_bases")
+        return e, l
+
     def msm_bases_load(self, group, bases, n, window_bits=0):
         h = C.c_void_p()
         self._check(self.lib.zkmi_msm_bases_load(self.h, group, _ptr(bases), n, window_bits,
@@ -254,6 +270,9 @@ class Context:
         return dict(zip(("g1_windows", "g1_entries_per_base", "g2_windows", "g2_entries_per_base",
                          "g1_table_bytes", "g2_table_bytes", "g1_shared", "g2_shared",
                          "g1_comb_k", "g2_comb_k"), [int(x) for x in arr]))
+
+    def pk_folded(self, h) -> bool:
+        return bool(self.lib.zkmi_pk_folded(h))
 
     def pk_free(self, h):
         self.lib.zkmi_pk_free(self.h, h)

@@ -28,6 +28,7 @@ extern "C" {
 typedef struct zkmi_ctx zkmi_ctx;
 typedef struct zkmi_pk zkmi_pk;
 typedef struct zkmi_cs zkmi_cs;
+typedef struct zkmi_r1cs_desc zkmi_r1cs_desc; /* defined with zkmi_r1cs_load below */
 
 enum zkmi_status {
   ZKMI_OK = 0,
@@ -80,6 +81,17 @@ int zkmi_ntt_batch(zkmi_ctx* ctx, void* data, int log_n, size_t batch, int inver
  * h_out: batch x 2^log_n coefficients, natural order. */
 int zkmi_h_batch(zkmi_ctx* ctx, const void* a, const void* b, const void* c, void* h_out,
                  int log_n, size_t batch);
+/* Parity hooks of the quotient in evaluation form (zkmi_pk_desc.fold_r1cs), conventions of
+ * zkmi_h_batch.  out: batch x 2^log_n, the evaluations of a.b on the coset 5<w>, natural order:
+ * coset FFT of the inverse FFT of a, times the same of b (log_n >= 8). */
+int zkmi_ab_coset_batch(zkmi_ctx* ctx, const void* a, const void* b, void* out, int log_n,
+                        size_t batch);
+/* The bases that a folded key puts in the place of pk.G1.Z, from the first 2^log_n - 1 points of
+ * g1_z (n_z >= 2^log_n - 1; Z_(n-1) = infinity), n = 2^log_n affine points each, on the host:
+ *   e_out[i] = den / n . sum_k 5^-k w^-ik Z_k,  l_out[i] = 1 / n . sum_k w^-ik Z_k,
+ *   den = 1 / (5^n - 1). */
+int zkmi_quotient_bases(zkmi_ctx* ctx, const void* g1_z, size_t n_z, int log_n, void* e_out,
+                        void* l_out);
 
 /* Fixed-base MSM handle: bases are uploaded once and expanded into HBM-resident tables of signed
  * window multiples.  group: 1 = G1, 2 = G2.
@@ -191,6 +203,22 @@ typedef struct {
    * the private committed wires and the commitment wires out of pk.G1.K, as gnark's setup does. */
   uint32_t n_commitments;
   const zkmi_commitment_desc* commitments;
+  /* Quotient in evaluation form; NULL = off.  The constraint system the key belongs to (a host
+   * struct; only n_wires, n_constraints, n_coeffs, coeffs, o_ptr and o_terms are read).  The prover's
+   * sum_k h_k Z_k is linear in the evaluations of a.b on the coset and in c, and c = O.w is linear in
+   * the wires, so the change of basis is applied once, here, to the bases: pk.G1.Z becomes its
+   * 2^log_n-point image E and every G1.K base takes the share of its wire's O column (ONE and the
+   * public wires that O touches get bases of their own).  Proving then needs neither the transform
+   * of c nor the final inverse transform.  The key is folded when log_n >= 8, n_commitments = 0 and
+   * the system's n_wires / n_constraints fit the key; otherwise it loads as without this field
+   * (zkmi_pk_folded tells).  A malformed system (the checks of zkmi_r1cs_load) is ZKMI_ERR_ARG.
+   * With a folded key:
+   *   - the c given to zkmi_prove_witness_submit(r1cs = NULL, ...) is ignored; c must be O.w, which
+   *     gnark's solution.C is, and the system proved must be the one given here;
+   *   - proofs of satisfied witnesses are byte for byte those of the unfolded key; the proofs of
+   *     unsatisfied witnesses, which are flagged in status_out and never valid, are other bytes
+   *     than the unfolded key writes. */
+  const zkmi_r1cs_desc* fold_r1cs;
 } zkmi_pk_desc;
 /* Copies the key to the device and builds the MSM window tables; host buffers may be freed
  * afterwards.  One-off per circuit (gnark's icicle backend does the same lazily). */
@@ -201,6 +229,8 @@ void zkmi_pk_free(zkmi_ctx* ctx, zkmi_pk* pk);
  * four MSMs), [5] = G2 table bytes, [6] / [7] = 1 when the G1 / G2 tables are shared-table plans,
  * [8] / [9] = group size k of the G1 / G2 comb tables (0 otherwise; then [0] / [2] = 254). */
 int zkmi_pk_info(const zkmi_pk* pk, uint64_t* info /* 10 */);
+/* 1 when the key was loaded with its quotient bases in evaluation form (fold_r1cs), else 0. */
+int zkmi_pk_folded(const zkmi_pk* pk);
 
 /* -- constraint system (witness program) ----------------------------------------------------- */
 /* What cs.R1CS.Solve needs, in the scheduled form produced by
@@ -285,7 +315,7 @@ typedef struct {
   uint32_t coeff; /* index into coeffs */
   uint32_t wire;  /* column: 0 = ONE, then public, secret, internal wires */
 } zkmi_term;
-typedef struct {
+struct zkmi_r1cs_desc {
   uint32_t n_wires, n_constraints, n_coeffs;
   const void* coeffs; /* n_coeffs fr elements, Montgomery, reduced */
   const uint32_t* l_ptr;
@@ -294,7 +324,7 @@ typedef struct {
   const zkmi_term* r_terms;
   const uint32_t* o_ptr;
   const zkmi_term* o_terms;
-} zkmi_r1cs_desc;
+};
 typedef struct zkmi_r1cs zkmi_r1cs;
 /* Validates every index on the host, copies the matrices to the device; host buffers may be freed
  * afterwards. */
@@ -310,6 +340,7 @@ void zkmi_r1cs_free(zkmi_ctx* ctx, zkmi_r1cs* r1cs);
  *          a, b, c and checks a.b = c (per-proof ZKMI_ERR_UNSATISFIED in collect's status_out)
  *   r1cs == NULL: a, b, c: batch x n_constraints fr elements each (<L_k,w>, <R_k,w>, <O_k,w>,
  *          solution.A/B/C); taken as they are (status_out = 0); the library pads to the domain
+ *          (a key folded with zkmi_pk_desc.fold_r1cs does not read c: it must be O.w of that system)
  *   rs: batch x 2 fr, as zkmi_prove_batch
  * Pageable host arrays have been consumed when the call returns; page-locked and device arrays
  * must stay valid until the matching collect. */
@@ -465,7 +496,7 @@ int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const 
 
 /* Per-stage device time of the last zkmi_prove_collect / zkmi_prove_batch in milliseconds, from
  * HIP events on the library's streams: [0] solve (stage 1, second stream), [1] quotient (NTTs +
- * pointwise), [2] G1 MSMs, [3] G2 MSM, [4] assembly (third stream; overlaps the next batch's
+ * pointwise; with a folded key the transforms of a and b alone), [2] G1 MSMs, [3] G2 MSM, [4] assembly (third stream; overlaps the next batch's
  * quotient when one is submitted), [5] main-stream span = [1] + [2] + [3] + delta multiples,
  * [6] sum over the four G1 msm_accumulate launches alone (one event pair around each launch),
  * [7] the G2 msm_accumulate launch alone.  With comb tables a pair also brackets the launch that

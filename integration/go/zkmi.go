@@ -80,6 +80,8 @@ type Key struct {
 	commitWires   []int // CommitmentIndex of every commitment
 	privateWires  [][]int
 	publicAndComm [][]int
+	// Folded: the key was loaded with its quotient bases in evaluation form (zkmi_pk_folded)
+	Folded bool
 }
 
 // LoadKey uploads a gnark proving key.  maxBatch sizes the HBM plan (zkmi_pk_desc.max_batch);
@@ -149,11 +151,39 @@ func (d *Device) LoadKey(pk *groth16_bn254.ProvingKey, ccs *cs_bn254.R1CS, maxBa
 		key.nCommitments = n
 	}
 
+	// Quotient in evaluation form (zkmi_pk_desc.fold_r1cs): with the O matrix and cs.Coefficients the
+	// library applies the quotient's change of basis to pk.G1.Z and folds c = O.w into pk.G1.K once,
+	// here, instead of transforming every batch.  Keys with commitments and domains below 2^8 load
+	// unfolded (Key.Folded tells).  A folded key ignores the C of ProveWitness: it must be O.w, which
+	// gnark's solution.C is.
+	fold := (*C.zkmi_r1cs_desc)(C.calloc(1, C.size_t(unsafe.Sizeof(C.zkmi_r1cs_desc{}))))
+	defer C.free(unsafe.Pointer(fold))
+	oPtr := make([]uint32, 1, ccs.GetNbConstraints()+1)
+	var oTerms []C.zkmi_term
+	if key.nCommitments == 0 && len(ccs.Coefficients) > 0 {
+		for _, c := range ccs.GetR1Cs() {
+			for _, t := range c.O {
+				oTerms = append(oTerms, C.zkmi_term{coeff: C.uint32_t(t.CID), wire: C.uint32_t(t.VID)})
+			}
+			oPtr = append(oPtr, uint32(len(oTerms)))
+		}
+		if len(oPtr) > 1 && len(oTerms) > 0 {
+			fold.n_wires = desc.n_wires
+			fold.n_constraints = C.uint32_t(len(oPtr) - 1)
+			fold.n_coeffs = C.uint32_t(len(ccs.Coefficients))
+			fold.coeffs = p(unsafe.Pointer(&ccs.Coefficients[0]))
+			fold.o_ptr = (*C.uint32_t)(p(unsafe.Pointer(&oPtr[0])))
+			fold.o_terms = (*C.zkmi_term)(p(unsafe.Pointer(&oTerms[0])))
+			desc.fold_r1cs = fold
+		}
+	}
+
 	d.mu.Lock()
 	defer d.mu.Unlock()
 	if rc := C.zkmi_pk_load(d.ctx, desc, &key.h); rc != 0 {
 		return nil, d.lastError()
 	}
+	key.Folded = C.zkmi_pk_folded(key.h) != 0
 	return key, nil
 }
 
