@@ -409,7 +409,7 @@ void zkmi_destroy(zkmi_ctx* ctx) {
     for (DevBuf* b : {&st.slots, &st.a, &st.b, &st.c, &st.misc, &st.sums, &st.commit})
       if (b->p) hipFree(b->p);
   for (DevBuf* b : {&ctx->ntt_tmp, &ctx->build_tmp, &ctx->msm_digits, &ctx->msm_sint,
-                    &ctx->msm_part[0], &ctx->msm_part[1], &ctx->side_part2, &ctx->side_part3})
+                    &ctx->msm_rowvar, &ctx->msm_part[0], &ctx->msm_part[1], &ctx->side_part2, &ctx->side_part3})
     if (b->p) hipFree(b->p);
   witness_ring_free(ctx);
   for (auto& e : ctx->ev)
@@ -588,9 +588,9 @@ int zkmi_ab_coset_batch(zkmi_ctx* ctx, const void* a, const void* b, void* out, 
 // summing to exactly 255 bits); 2..16 = uniform windows of that width.  If the table cannot be
 // allocated the plan is relaxed (more, narrower windows) until it fits.
 static int bases_load_plan(zkmi_ctx* ctx, int group, const void* bases_dev, size_t n, WinPlan plan,
-                           bool may_relax, zkmi_msm_bases** out) {
+                           bool may_relax, zkmi_msm_bases** out, int image = MSM_IMAGE_STD) {
   for (;;) {
-    int rc = msm_bases_build(ctx, group, bases_dev, n, plan, out);
+    int rc = msm_bases_build(ctx, group, bases_dev, n, plan, out, image);
     if (rc != ZKMI_ERR_OOM || !may_relax) return rc;
     if (plan.comb) {
       if (plan.comb <= 8) return rc;
@@ -653,8 +653,17 @@ static double usable_table_bytes_standalone(size_t n) {
 
 int zkmi_msm_bases_load(zkmi_ctx* ctx, int group, const void* bases, size_t n, int window_bits,
                         zkmi_msm_bases** out) {
+  return zkmi_msm_bases_load_image(ctx, group, bases, n, window_bits, 0, out);
+}
+
+int zkmi_msm_bases_load_image(zkmi_ctx* ctx, int group, const void* bases, size_t n,
+                              int window_bits, int image, zkmi_msm_bases** out) {
   ZK_HIP(hipSetDevice(ctx->device));
   if (!out) return ZKMI_ERR_ARG;
+  if (image != 0 && image != 1) {
+    ctx->err = "image must be 0 (x * 2^256) or 1 (x * 2^261)";
+    return ZKMI_ERR_ARG;
+  }
   if (!window_bits_ok(window_bits)) {
     ctx->err = "window_bits must be 0 (auto), in [2,16], 100 + [4,16], 200 + [2,20] or 300 + [3,21]";
     return ZKMI_ERR_ARG;
@@ -682,7 +691,8 @@ int zkmi_msm_bases_load(zkmi_ctx* ctx, int group, const void* bases, size_t n, i
       if ((double)COMB_W / k < (double)plan.W) plan = plan_comb(k, group == 1 ? s1 : s2);
     }
   }
-  return bases_load_plan(ctx, group, sb.dev, n, plan, window_bits == 0, out);
+  return bases_load_plan(ctx, group, sb.dev, n, plan, window_bits == 0, out,
+                         image ? MSM_IMAGE_F : MSM_IMAGE_STD);
 }
 
 void zkmi_msm_bases_free(zkmi_ctx* ctx, zkmi_msm_bases* b) {
@@ -719,6 +729,58 @@ int zkmi_msm_batch(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const void* scala
   ZK_HIP(hipMemcpyAsync(so.dev, aff, batch * pt, hipMemcpyDeviceToDevice, ctx->stream));
   if ((rc = so.finish())) return rc;
   ZK_HIP(hipStreamSynchronize(ctx->stream));
+  return ZKMI_OK;
+}
+
+int zkmi_msm_batch_rows(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const void* scalars,
+                        size_t n_rows, const uint32_t* row_idx, size_t batch, int image, int uniform,
+                        void* out) {
+  ZK_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
+  if (batch == 0) return ZKMI_OK;
+  const size_t n = bases->n, Bp = round_up(batch, 64);
+  if ((image != 0 && image != 1) || uniform < 0 || uniform > 2 || n_rows == 0) {
+    ctx->err = "msm_batch_rows: image in {0, 1}, uniform in {0, 1, 2}, n_rows > 0";
+    return ZKMI_ERR_ARG;
+  }
+  std::vector<uint32_t> idx(n);
+  if (row_idx) {
+    if (n && hipMemcpy(idx.data(), row_idx, n * sizeof(uint32_t), hipMemcpyDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "msm_batch_rows: cannot read row_idx";
+      return ZKMI_ERR_ARG;
+    }
+  } else {
+    for (size_t i = 0; i < n; i++) idx[i] = (uint32_t)i;
+  }
+  // every row number is range-checked on the host before a kernel uses it
+  for (uint32_t r : idx)
+    if (r >= n_rows) {
+      ctx->err = "msm_batch_rows: row_idx holds a row >= n_rows";
+      return ZKMI_ERR_ARG;
+    }
+  const size_t pt = bases->group == 1 ? 64 : 128;
+  Staged ss(ctx), so(ctx), si(ctx);
+  if ((rc = ss.in(scalars, batch * n_rows * 32)) || (rc = so.out(out, batch * pt)) ||
+      (rc = si.in(idx.data(), n * sizeof(uint32_t))))
+    return rc;
+  void *sbi, *acc, *aff, *flags = nullptr;
+  if ((rc = ensure_scratch(ctx, ctx->sets[0].a, n_rows * Bp * 32, &sbi)) ||
+      (rc = ensure_scratch(ctx, ctx->sets[0].b, Bp * pt * 2, &acc)) ||
+      (rc = ensure_scratch(ctx, ctx->sets[0].c, Bp * pt, &aff)))
+    return rc;
+  if ((rc = transpose_in(ctx, ss.dev, sbi, n_rows, batch, Bp, 32))) return rc;
+  if (uniform == 1 && ((rc = ensure_scratch(ctx, ctx->msm_rowvar, n_rows, &flags)) ||
+                       (rc = msm_rows_vary(ctx, (const Fr*)sbi, n_rows, Bp, batch, (uint8_t*)flags))))
+    return rc;
+  if ((rc = msm_run(ctx, bases, (const Fr*)sbi, (const uint32_t*)si.dev, Bp, batch, acc, image == 1,
+                    nullptr, nullptr, (const uint8_t*)flags, uniform == 2)))
+    return rc;
+  if ((rc = xyzz_to_affine(ctx, bases->group, acc, aff, Bp))) return rc;
+  ZK_HIP(hipMemcpyAsync(so.dev, aff, batch * pt, hipMemcpyDeviceToDevice, ctx->stream));
+  if ((rc = so.finish())) return rc;
+  ZK_HIP(hipStreamSynchronize(ctx->stream));   // idx is read by the queued copy until here
   return ZKMI_OK;
 }
 
@@ -968,23 +1030,29 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
       p1z = plan_comb(kz, sz);
     }
   }
+  // The wire MSMs read the value file, which the solver leaves in the F image; the quotient MSM
+  // reads h (or the coset evaluations of a folded key), which the NTT leaves in gnark's: sign-
+  // pattern tables are built native to those, so that the digit pass reads both as they are.
+  // (A batch that enters with gnark-image wires pays one conversion pass per wire MSM.)
   auto load = [&](int group, const void* pts, size_t n, const WinPlan& plan, bool relax,
-                  zkmi_msm_bases** out) -> int {
+                  zkmi_msm_bases** out, int image) -> int {
     Staged sb(ctx);
     int r = sb.in(pts, n * (group == 1 ? 64 : 128));
     if (r) return r;
-    r = bases_load_plan(ctx, group, sb.dev, n, plan, relax, out);
+    r = bases_load_plan(ctx, group, sb.dev, n, plan, relax, out, image);
     if (!r) (*out)->chunk_factor = d->msm_chunk_factor;
     return r;
   };
   if ((rc = upload_u32(ctx, wa.data(), d->n_a, &pk->a_wire)) ||
       (rc = upload_u32(ctx, wb.data(), d->n_b, &pk->b_wire)) ||
       (rc = upload_u32(ctx, fold.folded ? fold.k_wire.data() : wk.data(), n_kb, &pk->k_wire)) ||
-      (rc = load(1, d->g1_a, d->n_a, p1, auto1, &pk->A)) ||
-      (rc = load(1, d->g1_b, d->n_b, p1, auto1, &pk->B1)) ||
-      (rc = load(1, fold.folded ? (const void*)fold.k.data() : d->g1_k, n_kb, p1, auto1, &pk->K)) ||
-      (rc = load(1, fold.folded ? (const void*)fold.e.data() : d->g1_z, n_zb, p1z, auto1, &pk->Z)) ||
-      (rc = load(2, d->g2_b, d->n_b, p2, auto2, &pk->B2))) {
+      (rc = load(1, d->g1_a, d->n_a, p1, auto1, &pk->A, MSM_IMAGE_F)) ||
+      (rc = load(1, d->g1_b, d->n_b, p1, auto1, &pk->B1, MSM_IMAGE_F)) ||
+      (rc = load(1, fold.folded ? (const void*)fold.k.data() : d->g1_k, n_kb, p1, auto1, &pk->K,
+                 MSM_IMAGE_F)) ||
+      (rc = load(1, fold.folded ? (const void*)fold.e.data() : d->g1_z, n_zb, p1z, auto1, &pk->Z,
+                 MSM_IMAGE_STD)) ||
+      (rc = load(2, d->g2_b, d->n_b, p2, auto2, &pk->B2, MSM_IMAGE_F))) {
     zkmi_pk_free(ctx, pk);
     return rc;
   }
@@ -1242,15 +1310,31 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
   const bool d1 = pk->Z->plan.shared || pk->Z->plan.comb;
   const bool d2 = pk->B2->plan.shared || pk->B2->plan.comb;
   hipStream_t q3 = ctx->stream3;
-  if ((rc = msm_run(ctx, pk->A, slots, pk->a_wire, Bp, batch, v.sA, fd, d1 ? v.w1[0] : nullptr, q3)) ||
-      (rc = msm_run(ctx, pk->B1, slots, pk->b_wire, Bp, batch, v.sB1, fd, d1 ? v.w1[1] : nullptr, q3)) ||
-      (rc = msm_run(ctx, pk->K, slots, pk->k_wire, Bp, batch, v.sK, fd, d1 ? v.w1[2] : nullptr, q3)) ||
-      (rc = msm_run(ctx, pk->Z, h, nullptr, Bp, batch, v.sZ, false, d1 ? v.w1[3] : nullptr, q3))) {
+  // comb plans: A, B1, K and B2 walk overlapping rows of the value file, so which wires vary over
+  // the batch is found once for all four; the quotient's scalars are dense
+  uint8_t* rv = nullptr;
+  if (pk->A->plan.comb || pk->B2->plan.comb) {
+    void* p;
+    if ((rc = ensure_scratch(ctx, ctx->msm_rowvar, pk->n_wires, &p)) ||
+        (rc = msm_rows_vary(ctx, slots, pk->n_wires, Bp, batch, (uint8_t*)p))) {
+      ctx->msm_ev_set = -1;
+      return rc;
+    }
+    rv = (uint8_t*)p;
+  }
+  if ((rc = msm_run(ctx, pk->A, slots, pk->a_wire, Bp, batch, v.sA, fd, d1 ? v.w1[0] : nullptr, q3,
+                    rv)) ||
+      (rc = msm_run(ctx, pk->B1, slots, pk->b_wire, Bp, batch, v.sB1, fd, d1 ? v.w1[1] : nullptr, q3,
+                    rv)) ||
+      (rc = msm_run(ctx, pk->K, slots, pk->k_wire, Bp, batch, v.sK, fd, d1 ? v.w1[2] : nullptr, q3,
+                    rv)) ||
+      (rc = msm_run(ctx, pk->Z, h, nullptr, Bp, batch, v.sZ, false, d1 ? v.w1[3] : nullptr, q3,
+                    nullptr, true))) {
     ctx->msm_ev_set = -1;
     return rc;
   }
   hipEventRecord(S.evq[2], ctx->stream);
-  rc = msm_run(ctx, pk->B2, slots, pk->b_wire, Bp, batch, v.sB2, fd, d2 ? v.w2 : nullptr, q3);
+  rc = msm_run(ctx, pk->B2, slots, pk->b_wire, Bp, batch, v.sB2, fd, d2 ? v.w2 : nullptr, q3, rv);
   ctx->msm_ev_set = -1;
   if (rc) return rc;
   hipEventRecord(S.evq[3], ctx->stream);

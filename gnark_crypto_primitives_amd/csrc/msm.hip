@@ -146,12 +146,13 @@ WinPlan plan_windows_for_budget(size_t n_total, int group, double budget_bytes) 
 }
 
 // the G2 side of the table builds and of the launch routines is instantiated in msm_g2.hip
-extern template int build_comb<Fq2>(zkmi_ctx*, const Affine<Fq2>*, size_t, const WinPlan&,
+extern template int build_comb<Fq2>(zkmi_ctx*, const Affine<Fq2>*, size_t, const WinPlan&, int,
                                     Affine<Fq2>*, int*, Affine<Fq2>*);
 extern template int build_impl<Fq2>(zkmi_ctx*, const Affine<Fq2>*, size_t, const WinPlan&,
                                     Affine<Fq2>*);
 extern template int run_impl<Fq2>(zkmi_ctx*, const zkmi_msm_bases*, const Fr*, const uint32_t*,
-                                  size_t, size_t, XYZZ<Fq2>*, bool, XYZZ<Fq2>*, hipStream_t);
+                                  size_t, size_t, XYZZ<Fq2>*, bool, XYZZ<Fq2>*, hipStream_t,
+                                  const uint8_t*, bool);
 
 // fn(F{}) with the coordinate field of the group: Fq for G1, Fq2 for G2
 template <class Fn>
@@ -160,7 +161,7 @@ static auto by_group(int group, Fn&& fn) {
 }
 
 int msm_bases_build(zkmi_ctx* ctx, int group, const void* bases_dev, size_t n, const WinPlan& plan,
-                    zkmi_msm_bases** out) {
+                    zkmi_msm_bases** out, int image) {
   if (group != 1 && group != 2) {
     ctx->err = "group must be 1 (G1) or 2 (G2)";
     return ZKMI_ERR_ARG;
@@ -169,6 +170,7 @@ int msm_bases_build(zkmi_ctx* ctx, int group, const void* bases_dev, size_t n, c
   b->group = group;
   b->n = n;
   b->plan = plan;
+  b->image = image;
   const size_t entry = group == 1 ? sizeof(G1Affine) : sizeof(G2Affine);
   b->n_groups = plan.comb ? (n + plan.comb - 1) / plan.comb : 0;
   b->table_bytes = plan.comb ? b->n_groups * ((size_t)1 << (plan.comb - plan.comb_signed)) * entry
@@ -196,7 +198,7 @@ int msm_bases_build(zkmi_ctx* ctx, int group, const void* bases_dev, size_t n, c
     const Affine<F>* bases = (const Affine<F>*)bases_dev;
     hipLaunchKernelGGL((msm_inf_flags<F>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        ctx->stream, bases, (uint32_t)n, b->inf);
-    return plan.comb ? build_comb<F>(ctx, bases, n, plan, (Affine<F>*)b->table,
+    return plan.comb ? build_comb<F>(ctx, bases, n, plan, image, (Affine<F>*)b->table,
                                      &b->entries_may_be_inf, &stotal_of(b, f))
                      : build_impl<F>(ctx, bases, n, plan, (Affine<F>*)b->table);
   });
@@ -241,7 +243,7 @@ int msm_horner_run(zkmi_ctx* ctx, hipStream_t stream, int count,
 
 int msm_run(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, const uint32_t* row_idx,
             size_t Bp, size_t batch, void* out_xyzz, bool scalars_f, void* wsum_out,
-            hipStream_t finish_stream) {
+            hipStream_t finish_stream, const uint8_t* row_varies, bool dense) {
   return by_group(bases->group, [&](auto f) -> int {
     using F = decltype(f);
     if (bases->n == 0) {
@@ -258,8 +260,17 @@ int msm_run(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, const
       return ZKMI_ERR_ARG;
     }
     return run_impl<F>(ctx, bases, scalars, row_idx, Bp, batch, (XYZZ<F>*)out_xyzz, scalars_f,
-                       (XYZZ<F>*)wsum_out, finish_stream);
+                       (XYZZ<F>*)wsum_out, finish_stream, row_varies, dense);
   });
+}
+
+int msm_rows_vary(zkmi_ctx* ctx, const Fr* rows, size_t n_rows, size_t Bp, size_t batch,
+                  uint8_t* flags) {
+  if (n_rows == 0) return ZKMI_OK;
+  hipLaunchKernelGGL(rows_vary_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, ctx->stream,
+                     rows, (const uint32_t*)nullptr, (uint32_t)n_rows, Bp, batch, flags);
+  ZK_HIP(hipGetLastError());
+  return ZKMI_OK;
 }
 
 int xyzz_to_affine(zkmi_ctx* ctx, int group, const void* in, void* out, size_t n) {

@@ -6,6 +6,7 @@
 #pragma once
 #include "zkmi_internal.h"
 #include "ec29.h"
+#include "comb_sign.h"
 
 namespace zk {
 
@@ -412,6 +413,17 @@ __global__ void comb_total(const Affine<F>* __restrict__ gsum, uint32_t n_groups
   *out = to_affine(s);
 }
 
+// out[i] = c * bases[i], c a plain integer below r (wave-uniform): the bases of a sign-pattern table
+// native to a scalar image (build_comb), double-and-add from c's top bit, once per key
+template <class F>
+__global__ __launch_bounds__(64) void comb_scale_bases(const Affine<F>* __restrict__ bases,
+                                                       uint32_t n, Fr c,
+                                                       Affine<F>* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = to_affine(scalar_mul(bases[i], c.v));
+}
+
 // one thread per (group, segment of seg_len consecutive table indices).
 // Unsigned tables: entry m = sum of the bases whose bit is set in m (2^k entries, entry 0 unused).
 // SIGNED tables: entry e (k - 1 bits) = P_(k-1) + sum_{i < k-1} (e_i ? +P_i : -P_i): every k-bit
@@ -433,7 +445,7 @@ __global__ __launch_bounds__(64) void comb_build(const Affine<F>* __restrict__ b
   Affine<F>* seg = table + (size_t)g * per_group + m0;
   // entry of the first index of the segment; `live` = bases that exist and are finite (the
   // unsigned digit pass never sets the bit of any other base, so masks outside `live` are never
-  // gathered)
+  // gathered; the signed digit pass gathers every pattern, also in a group with no finite base)
   XYZZ<F> acc = XYZZ<F>::inf();
   uint32_t live = 0;
   for (uint32_t i = 0; i < k; i++) {
@@ -455,7 +467,7 @@ __global__ __launch_bounds__(64) void comb_build(const Affine<F>* __restrict__ b
   for (uint32_t d = 0; d < seg_len; d++) {
     const bool is_inf = acc.is_inf();
     const uint32_t m = m0 + d;
-    inf_seen = inf_seen || (is_inf && (SIGNED ? live != 0 : (m != 0 && (m & ~live) == 0)));
+    inf_seen = inf_seen || (is_inf && (SIGNED || (m != 0 && (m & ~live) == 0)));
     // an identity entry is stored as (0, 0) (0 stays 0 through the inversion and the domain change)
     if (is_inf)
       inv.push(seg, d, F::zero(), F::zero(), F::one(), F::one());
@@ -468,79 +480,74 @@ __global__ __launch_bounds__(64) void comb_build(const Affine<F>* __restrict__ b
   if (inf_seen) atomicOr(any_inf, 1);
 }
 
-// Montgomery scalars -> plain integers, same planar layout (row i of the output = base i).
+// Sign-pattern tables: every scalar is a sum of 254 signed powers of two.  With t the canonical
+// image of the scalar that the table is native to (bases->image; the bases were scaled by
+// (2 * 2^256)^-1 or (2 * 2^261)^-1 at the build, so that s P = 2 t P''):
+//   e = 1 if t is even;  t' = t + e (odd, <= r);  C = (t' + 2^254 - 1) / 2 < 2^254
+//   => t' = sum_j (2 C_j - 1) 2^j, and  s P = 2 (t' P'' - e P'').
+// Bit j of C is base i's sign in window j; the parities e are the sign pattern of one extra window
+// (index 254) whose sum is subtracted once at the end together with the sum of all scaled bases:
+//   sum_i s_i P_i = 2 H - W_254 - S,  H = sum_j 2^j W_j  (msm_horner_comb).
+// C and e are t's own bits (comb_sign.h): the digit pass reads the scalar rows as they are.
 //
-// SIGNED (sign-pattern tables): every scalar is rewritten as a sum of 254 signed powers of two.
-//   t = s / 2 mod r;  e = 1 if t is even;  t' = t + e (odd, <= r);  C = (t' + 2^254 - 1) / 2 < 2^254
-//   => t' = sum_j (2 C_j - 1) 2^j, and  s P = 2 (t' P - e P).
-// Bit j of C is base i's sign in window j; the parity e rides in bit 255 and becomes the sign
-// pattern of one extra window (index 254) whose sum is subtracted once at the end together with
-// the sum of all bases:  sum_i s_i P_i = 2 H - W_254 - S,  H = sum_j 2^j W_j  (msm_horner_comb).
-//
-// gvar[g] (zeroed before the launch) is set to 1 when a scalar of group g = i / k differs from
-// lane 0's within the first `batch` lanes; padding lanes do not take part.  The raw Montgomery
-// words are compared: equal words convert to equal integers, so a group left at 0 has the same
-// digits in every proof of the batch (comb_split_kernel).
-template <bool SIGNED>
-__global__ __launch_bounds__(256) void comb_scalars_kernel(const Fr* __restrict__ scalars,
-                                                           const uint32_t* __restrict__ row_idx,
-                                                           size_t Bp, uint32_t n, int32_t kmul32,
-                                                           const uint8_t* __restrict__ inf,
-                                                           Fr* __restrict__ out, size_t batch,
-                                                           uint32_t k, uint32_t* __restrict__ gvar) {
+// What is left of a scalar pass, same planar layout (row i of the output = base i):
+//   * subset-sum tables: the Montgomery image -> the plain integer (kk = 32 or 1 in limb 0: small
+//     values stay small); the rows of bases at infinity are zeroed, their bits must stay clear;
+//   * sign-pattern tables whose scalars arrive in the other image: image -> native image
+//     (kk = 2^266 mod r for gnark's image on an F-native table, 2^256 mod r the other way round).
+static __global__ __launch_bounds__(256) void comb_scalars_kernel(const Fr* __restrict__ scalars,
+                                                                  const uint32_t* __restrict__ row_idx,
+                                                                  size_t Bp, uint32_t n, Fr29 kk,
+                                                                  const uint8_t* __restrict__ inf,
+                                                                  Fr* __restrict__ out) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (uint32_t i = blockIdx.y; i < n; i += gridDim.y) {
     Fr s = Fr::zero();
-    if (!inf[i]) {   // the point at infinity contributes nothing: its bits never matter
-      Fr29 kk = Fr29::zero();
-      kk.v[0] = kmul32;
+    if (!inf[i]) {   // wave-uniform
       const uint32_t row = row_idx ? row_idx[i] : i;
       const Fr raw = bi_ld(scalars, row, b, Bp);
-      const Fr raw0 = bi_ld(scalars, row, 0, Bp);   // wave-uniform
-      uint32_t diff = 0;
-#pragma unroll
-      for (int l = 0; l < 8; l++) diff |= raw.v[l] ^ raw0.v[l];
-      // one plain store per wave; waves that race write the same value
-      if (__ballot(b < batch && diff != 0) != 0 && (threadIdx.x & 63u) == 0) gvar[i / k] = 1u;
       pack_canonical<Fr29Params>(s.v, mul(unpack29<Fr29Params>(raw.v), kk));
-      if (SIGNED) {
-        // t = (s + (s odd ? r : 0)) >> 1      (s + r < 2^255)
-        const uint32_t odd = s.v[0] & 1u;
-        uint64_t cy = 0;
-#pragma unroll
-        for (int l = 0; l < 8; l++) {
-          cy += (uint64_t)s.v[l] + (odd ? FrParams::p(l) : 0u);
-          s.v[l] = (uint32_t)cy;
-          cy >>= 32;
-        }
-#pragma unroll
-        for (int l = 0; l < 7; l++) s.v[l] = (s.v[l] >> 1) | (s.v[l + 1] << 31);
-        s.v[7] >>= 1;
-        const uint32_t e = (s.v[0] & 1u) ^ 1u;
-        // C = (t' - 1 + 2^254) >> 1 with t' = t + e = t | 1 (odd), so t' - 1 = t with bit 0 cleared;
-        // t' <= r < 2^254: the sum stays below 2^255
-        s.v[0] &= ~1u;
-        cy = 0;
-#pragma unroll
-        for (int l = 0; l < 8; l++) {
-          cy += (uint64_t)s.v[l] + (l == 7 ? 0x40000000u : 0u);   // + 2^254
-          s.v[l] = (uint32_t)cy;
-          cy >>= 32;
-        }
-#pragma unroll
-        for (int l = 0; l < 7; l++) s.v[l] = (s.v[l] >> 1) | (s.v[l + 1] << 31);
-        s.v[7] = (s.v[7] >> 1) | (e << 31);
-      }
     }
     bi_st(out, i, b, Bp, s);
   }
 }
 
-// Splits the groups by gvar: vlist / ulist = the varying / uniform groups in increasing order,
+// flags[i] = 1 when row (row_idx ? row_idx[i] : i) of `scalars` differs from its lane 0 within the
+// first `batch` lanes, else 0; padding lanes do not take part.  The raw words are compared: equal
+// words have equal digits in whatever image they are read, so a comb group whose rows are all
+// flagged 0 has the same digits in every proof of the batch (comb_split_kernel).  One wave per
+// row, which stops at the first 64 lanes that differ; one plain store per wave, every flag written.
+static __global__ __launch_bounds__(256) void rows_vary_kernel(const Fr* __restrict__ scalars,
+                                                               const uint32_t* __restrict__ row_idx,
+                                                               uint32_t n_rows, size_t Bp,
+                                                               size_t batch,
+                                                               uint8_t* __restrict__ flags) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // wave-uniform
+  if (i >= n_rows) return;
+  const uint32_t row = row_idx ? row_idx[i] : i;
+  const Fr raw0 = bi_ld(scalars, row, 0, Bp);   // wave-uniform
+  bool var = false;
+  for (size_t b0 = 0; b0 < batch && !var; b0 += 64) {
+    const size_t b = b0 + lane;   // < Bp: batch <= Bp, a multiple of 64
+    const Fr raw = bi_ld(scalars, row, b, Bp);
+    uint32_t diff = 0;
+#pragma unroll
+    for (int l = 0; l < 8; l++) diff |= raw.v[l] ^ raw0.v[l];
+    var = __ballot(b < batch && diff != 0) != 0;
+  }
+  if (lane == 0) flags[i] = var ? 1 : 0;
+}
+
+// Splits the groups: a group varies when `dense` is set or a flag of one of its bases is
+// (flags[flag_idx ? flag_idx[i] : i] for base i: rows_vary_kernel's output per scalar row, or per
+// base).  vlist / ulist = the varying / uniform groups in increasing order,
 // vpos[g] = position of g in vlist (~0u: uniform), counts = {|vlist|, |ulist|}.  One workgroup of
 // 1024 threads walks the groups in tiles; the counts stay on the device (the accumulate and
 // common-sum grids are sized from n_groups and read them there).
-static __global__ __launch_bounds__(1024) void comb_split_kernel(const uint32_t* __restrict__ gvar,
+static __global__ __launch_bounds__(1024) void comb_split_kernel(const uint8_t* __restrict__ flags,
+                                                                 const uint32_t* __restrict__ flag_idx,
+                                                                 uint32_t n, uint32_t k, int dense,
                                                                  uint32_t n_groups,
                                                                  uint32_t* __restrict__ vlist,
                                                                  uint32_t* __restrict__ ulist,
@@ -552,7 +559,16 @@ static __global__ __launch_bounds__(1024) void comb_split_kernel(const uint32_t*
   for (uint32_t g0 = 0; g0 < n_groups; g0 += 1024) {
     const uint32_t g = g0 + t;
     const bool live = g < n_groups;
-    const bool var = live && gvar[g] != 0;
+    bool var = live && dense;
+    if (live && !dense) {
+      uint32_t any = 0;   // no early exit: the k lookups are independent loads
+#pragma unroll 8
+      for (uint32_t q = 0; q < k; q++) {
+        const size_t i = (size_t)g * k + q;
+        if (i < n) any |= flags[flag_idx ? flag_idx[i] : i];
+      }
+      var = any != 0;
+    }
     const unsigned long long vm = __ballot(var);
     if (lane == 0) wave_nv[w] = (uint32_t)__popcll(vm);
     __syncthreads();
@@ -583,12 +599,20 @@ static __global__ __launch_bounds__(1024) void comb_split_kernel(const uint32_t*
 
 // digits[j][p][b] = sum_i bit_j(s[gk+i][b]) << i for the varying group g = vlist[p].  SIGNED: k-bit
 // sign pattern M -> (index, negate): top bit set: entry M & (2^(k-1) - 1); clear: entry
-// ~M & (2^(k-1) - 1), negated (bit 31 of the digit).  Window 254 takes bit 255 of the rewritten
-// scalars (the parity pattern).  A uniform group has lane 0's digits in every proof: only the
+// ~M & (2^(k-1) - 1), negated (bit 31 of the digit).  SIGNED reads the table's native image t as
+// it is (base i's row is row_idx[i] of `sint`: the value file itself, or the converted rows):
+// comb_sign_window names the window of every bit of t, the bits of window 253 are all ones, and
+// rows past n read as zero.  The row of a base at infinity is read like any other: its bits select
+// between entries that are equal (or both the identity), whatever they are.
+// A uniform group has lane 0's digits in every proof: only the
 // first wave of the blocks at x = 0 transposes it, and lane 0 writes d0[j][g] (comb_common_sums).
+// Three waves per SIMD (at most 168 VGPRs, which the 21 x 4 loaded words and the 32 transposed ones
+// leave room for): the pass waits on memory, and at two waves it measured 1.4 x slower.
 template <int KMAX, bool SIGNED>
-__global__ __launch_bounds__(256) void comb_digits_kernel(const Fr* __restrict__ sint, size_t Bp,
-                                                          uint32_t n, uint32_t k, uint32_t n_groups,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void comb_digits_kernel(const Fr* __restrict__ sint,
+                                                          const uint32_t* __restrict__ row_idx,
+                                                          size_t Bp, uint32_t n, uint32_t k,
+                                                          uint32_t n_groups,
                                                           const uint32_t* __restrict__ vpos,
                                                           uint32_t* __restrict__ digits,
                                                           uint32_t* __restrict__ d0) {
@@ -599,14 +623,24 @@ __global__ __launch_bounds__(256) void comb_digits_kernel(const Fr* __restrict__
     const uint32_t p = vpos[g];
     const bool uni = p == ~0u;
     if (uni && (blockIdx.x != 0 || threadIdx.x >= 64)) continue;   // wave-uniform
+    if (SIGNED) {   // window 253: every sign is +, the entry of the all-ones pattern
+      if (!uni)
+        digits[((size_t)COMB_SIGN_ONES * n_groups + p) * Bp + b] = low;
+      else if (b == 0)
+        d0[(size_t)COMB_SIGN_ONES * n_groups + g] = low;
+    }
+    size_t rows[KMAX];   // wave-uniform
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) {
+      const size_t bi = (size_t)g * k + i;
+      rows[i] = (i < (int)k && bi < n) ? (row_idx ? (size_t)row_idx[bi] : bi) : ~(size_t)0;
+    }
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       uint4 wv[KMAX];
 #pragma unroll
-      for (int i = 0; i < KMAX; i++) {
-        const size_t bi = (size_t)g * k + i;
-        wv[i] = (i < (int)k && bi < n) ? base[(bi * 2 + h) * Bp + b] : make_uint4(0, 0, 0, 0);
-      }
+      for (int i = 0; i < KMAX; i++)
+        wv[i] = rows[i] != ~(size_t)0 ? base[(rows[i] * 2 + h) * Bp + b] : make_uint4(0, 0, 0, 0);
 #pragma unroll
       for (int c = 0; c < 4; c++) {
         // 32 x 32 bit transpose (rows = bases of the group, columns = 32 scalar bits): afterwards
@@ -630,13 +664,14 @@ __global__ __launch_bounds__(256) void comb_digits_kernel(const Fr* __restrict__
 #pragma unroll
         for (int bit = 0; bit < 32; bit++) {
           int j = (h * 4 + c) * 32 + bit;
+          bool comp = false;
           if (SIGNED) {
-            if (j == 254) continue;     // C < 2^254
-            if (j == 255) j = 254;      // parity pattern
+            j = comb_sign_window(h * 4 + c, bit, &comp);
+            if (j < 0) continue;        // t < 2^254
           } else if (j >= COMB_W) {
             break;
           }
-          uint32_t idx = m[bit];
+          uint32_t idx = comp ? ~m[bit] : m[bit];
           if (SIGNED) idx = ((idx >> (k - 1)) & 1u) ? (idx & low) : ((~idx & low) | 0x80000000u);
           if (!uni)
             digits[((size_t)j * n_groups + p) * Bp + b] = idx;
@@ -896,8 +931,19 @@ static BuildSlab build_slab(uint32_t seg_len, uint64_t n_rows) {
 template <class B> static auto& stotal_of(B* b, Fq) { return b->stotal1; }
 template <class B> static auto& stotal_of(B* b, Fq2) { return b->stotal2; }
 
+// (2 * 2^256)^-1 or (2 * 2^261)^-1 mod r as a plain integer: the factor on the bases of a
+// sign-pattern table native to gnark's image / the F image (comb_scalars_kernel's comment)
+static inline Fr comb_base_scale(int image) {
+  Fr x = Fr::one();   // 2^0 in Montgomery form
+  const int e = image == MSM_IMAGE_F ? 262 : 257;
+  for (int i = 0; i < e; i++) x = dbl(x);
+  return from_mont(inverse(x));
+}
+
+// Sign-pattern tables are built over the bases scaled by comb_base_scale(image), so stotal comes
+// out scaled as well; subset-sum tables over the bases as they are.
 template <class F>
-int build_comb(zkmi_ctx* ctx, const Affine<F>* bases_dev, size_t n, const WinPlan& plan,
+int build_comb(zkmi_ctx* ctx, const Affine<F>* bases_dev, size_t n, const WinPlan& plan, int image,
                Affine<F>* table, int* any_inf_host, Affine<F>* stotal_host) {
   const uint32_t k = plan.comb;
   const bool sg = plan.comb_signed != 0;
@@ -910,12 +956,20 @@ int build_comb(zkmi_ctx* ctx, const Affine<F>* bases_dev, size_t n, const WinPla
   void* scratch;
   const size_t dp_bytes = round_up(n_groups * k * sizeof(Affine<F>), 256);
   const size_t gs_bytes = round_up((n_groups + 1) * sizeof(Affine<F>), 256);
-  int rc = ensure_scratch(ctx, ctx->build_tmp, dp_bytes + gs_bytes + 256 + slab.bytes, &scratch);
+  const size_t sc_bytes = sg ? round_up(n * sizeof(Affine<F>), 256) : 0;
+  int rc = ensure_scratch(ctx, ctx->build_tmp, dp_bytes + gs_bytes + 256 + slab.bytes + sc_bytes,
+                          &scratch);
   if (rc) return rc;
   Affine<F>* dpts = (Affine<F>*)scratch;
   Affine<F>* gsum = (Affine<F>*)((char*)scratch + dp_bytes);
   int* any_inf = (int*)((char*)scratch + dp_bytes + gs_bytes);
   F* inv_scratch = (F*)((char*)scratch + dp_bytes + gs_bytes + 256);
+  if (sg) {
+    Affine<F>* scaled = (Affine<F>*)((char*)inv_scratch + slab.bytes);
+    hipLaunchKernelGGL((comb_scale_bases<F>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0,
+                       ctx->stream, bases_dev, (uint32_t)n, comb_base_scale(image), scaled);
+    bases_dev = scaled;
+  }
   ZK_HIP(hipMemsetAsync(any_inf, 0, sizeof(int), ctx->stream));
   hipLaunchKernelGGL((comb_prep<F>), dim3((unsigned)((n_groups + 63) / 64)), dim3(64), 0,
                      ctx->stream, bases_dev, (uint32_t)n, k, (uint32_t)n_groups, dpts, gsum,
@@ -1050,7 +1104,7 @@ static inline void acc_timer_end(zkmi_ctx* ctx, hipEvent_t end) {
 template <class F>
 int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, const uint32_t* row_idx,
              size_t Bp, size_t batch, XYZZ<F>* out, bool scalars_f, XYZZ<F>* wsum_out,
-             hipStream_t finish_stream) {
+             hipStream_t finish_stream, const uint8_t* row_varies, bool dense) {
   const size_t n = bases->n;
   const uint32_t k = bases->plan.comb;
   const bool sg = bases->plan.comb_signed != 0;
@@ -1073,32 +1127,52 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
   // buffers -- correct, no gain: the pass is ALU work like the accumulate kernel it would hide
   // under, which slowed down by exactly the pass's 7 ms.)
   // digits [W][G][Bp] (the first |vlist| rows of every window are used), then lane 0's digits of
-  // the uniform groups [W][G] and the split of the groups: gvar, vlist, ulist, vpos [G]
+  // the uniform groups [W][G], the split of the groups: vlist, ulist, vpos [G], and the flags of
+  // the bases [n] when the caller brings none
   if ((rc = ensure_scratch(ctx, ctx->msm_digits,
-                           ((size_t)W * G * Bp + (size_t)(W + 4) * G) * sizeof(uint32_t),
+                           ((size_t)W * G * Bp + (size_t)(W + 3) * G) * sizeof(uint32_t) + n,
                            &digits)))
     return rc;
-  if ((rc = ensure_scratch(ctx, ctx->msm_sint, n * Bp * sizeof(Fr), &sint))) return rc;
   uint32_t* d0 = (uint32_t*)digits + (size_t)W * G * Bp;
-  uint32_t* gvar = d0 + (size_t)W * G;
-  uint32_t* vlist = gvar + G;
+  uint32_t* vlist = d0 + (size_t)W * G;
   uint32_t* ulist = vlist + G;
   uint32_t* vpos = ulist + G;
   const PartView<F> pv(part, cs, W, Bp);
   uint32_t* counts = pv.counts;
   XYZZ<F>* wsum = wsum_out ? wsum_out : pv.wsum;
   const unsigned bx = (Bp % 256 == 0) ? 256 : 64;
-  const dim3 sgrid((unsigned)(Bp / bx), (unsigned)(n < 16384 ? n : 16384));
   const dim3 dgrid((unsigned)(Bp / bx), (unsigned)(G < 8192 ? G : 8192));
-  const int32_t km = (int32_t)(scalars_f ? 1 : 32);
-  ZK_HIP(hipMemsetAsync(gvar, 0, G * sizeof(uint32_t), ctx->stream));
-  hipLaunchKernelGGL((sg ? comb_scalars_kernel<true> : comb_scalars_kernel<false>), sgrid, dim3(bx), 0,
-                     ctx->stream, scalars, row_idx, Bp, (uint32_t)n, km, (const uint8_t*)bases->inf,
-                     (Fr*)sint, batch, k, gvar);
-  hipLaunchKernelGGL(comb_split_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)gvar,
-                     (uint32_t)G, vlist, ulist, vpos, counts);
+  // which groups vary: from the caller's flags per scalar row, or from the scalars as they arrive
+  const uint8_t* flags = row_varies;
+  const uint32_t* flag_idx = row_idx;
+  if (!flags && !dense) {
+    uint8_t* own = (uint8_t*)(vpos + G);
+    hipLaunchKernelGGL(rows_vary_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream,
+                       scalars, row_idx, (uint32_t)n, Bp, batch, own);
+    flags = own;
+    flag_idx = nullptr;
+  }
+  hipLaunchKernelGGL(comb_split_kernel, dim3(1), dim3(1024), 0, ctx->stream, flags, flag_idx,
+                     (uint32_t)n, k, dense ? 1 : 0, (uint32_t)G, vlist, ulist, vpos, counts);
+  // what the digit pass reads: the scalar rows themselves when a sign-pattern table is native to
+  // their image, else one pass writes the plain integers (subset sums) or the native image
+  const Fr* dsrc = scalars;
+  const uint32_t* didx = row_idx;
+  if (!(sg && scalars_f == (bases->image == MSM_IMAGE_F))) {
+    if ((rc = ensure_scratch(ctx, ctx->msm_sint, n * Bp * sizeof(Fr), &sint))) return rc;
+    Fr29 kk = Fr29::zero();
+    if (!sg)
+      kk.v[0] = scalars_f ? 1 : 32;
+    else
+      for (int i = 0; i < 9; i++) kk.v[i] = scalars_f ? Fr29Params::c256(i) : Fr29Params::c266(i);
+    const dim3 sgrid((unsigned)(Bp / bx), (unsigned)(n < 16384 ? n : 16384));
+    hipLaunchKernelGGL(comb_scalars_kernel, sgrid, dim3(bx), 0, ctx->stream, scalars, row_idx, Bp,
+                       (uint32_t)n, kk, (const uint8_t*)bases->inf, (Fr*)sint);
+    dsrc = (const Fr*)sint;
+    didx = nullptr;
+  }
   hipLaunchKernelGGL((sg ? comb_digits_kernel<21, true> : comb_digits_kernel<20, false>), dgrid,
-                     dim3(bx), 0, ctx->stream, (const Fr*)sint, Bp, (uint32_t)n, k, (uint32_t)G,
+                     dim3(bx), 0, ctx->stream, dsrc, didx, Bp, (uint32_t)n, k, (uint32_t)G,
                      (const uint32_t*)vpos, (uint32_t*)digits, d0);
   // timed: the common sums and the accumulate launch, every mixed addition
   const hipEvent_t timed = acc_timer_begin(ctx, bases);
@@ -1236,10 +1310,10 @@ int run_windows(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
 template <class F>
 int run_impl(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
              const uint32_t* row_idx, size_t Bp, size_t batch, XYZZ<F>* out, bool scalars_f,
-             XYZZ<F>* wsum_out, hipStream_t finish_stream) {
+             XYZZ<F>* wsum_out, hipStream_t finish_stream, const uint8_t* row_varies, bool dense) {
   if (bases->plan.comb)
     return run_comb<F>(ctx, bases, scalars, row_idx, Bp, batch, out, scalars_f, wsum_out,
-                       finish_stream);
+                       finish_stream, row_varies, dense);
   if (bases->plan.shared)
     return run_shared<F>(ctx, bases, scalars, row_idx, Bp, out, scalars_f, wsum_out);
   if (wsum_out) {

@@ -63,7 +63,8 @@ struct zkmi_ctx {
   // each other:
   zk::DevBuf ntt_tmp;                // NTT temporary of the quotient
   zk::DevBuf build_tmp;              // table-build inversion scratch; proof-of-knowledge temporary
-  zk::DevBuf msm_digits, msm_sint;   // MSM digits, integer scalars
+  zk::DevBuf msm_digits, msm_sint;   // MSM digits, converted scalars (comb_scalars_kernel)
+  zk::DevBuf msm_rowvar;             // which value-file rows vary over the batch (enqueue_heavy)
   zk::DevBuf msm_part[2];            // MSM chunk partials; [1] only for deferred tails (part_ev)
   // Side bases (zkmi_msm_bases::side) run while the main stream may be running an MSM on
   // msm_part[0], so each side stream has its own partials:
@@ -156,7 +157,11 @@ struct zkmi_msm_bases {
   size_t n_groups = 0;     // comb plans: ceil(n / k)
   int entries_may_be_inf = 0;  // comb plans: some subset of a group sums to the identity
   uint32_t chunk_factor = 0;   // (window, chunk) blocks in flight / wave slots; 0 = default
-  zk::G1Affine stotal1 = {};   // signed comb tables: sum of all bases (G1 / G2 by `group`)
+  // signed comb tables: the scalar image the table is native to (MSM_IMAGE_*: its bases were
+  // scaled so that the digit pass reads scalars of that image as they are), and the sum of all
+  // scaled bases (G1 / G2 by `group`)
+  int image = 0;
+  zk::G1Affine stotal1 = {};
   zk::G2Affine stotal2 = {};
   // side = 1: per-window plan run on the second stream (commitment MSMs of a submit, beside the
   // previous batch's MSMs on the main stream): its own partial-sum scratch, no deferred tails.
@@ -373,8 +378,15 @@ WinPlan plan_windows_for_budget(size_t n_total, int group, double budget_bytes);
 void plan_comb_for_budget(size_t n1, size_t n2, double usable_bytes, int* k1, int* k2, bool* sg1,
                           bool* sg2, bool allow_signed = true);
 void plan_shared_for_budget(size_t n1, size_t n2, double usable_bytes, int* c1, int* c2);
+// image: the canonical image most scalars of this base set will arrive in, gnark's (x * 2^256) or
+// the F domain (x * 2^261).  Only sign-pattern comb plans use it: their table is built over the
+// bases times (2 * 2^256)^-1 resp. (2 * 2^261)^-1 mod r, so that the signs of every window are
+// bits of the image itself (comb_sign.h) and scalars of that image need no pass of their own.
+// Scalars of the other image still work (one conversion pass); every other plan needs the plain
+// integer, in which small values stay small, and ignores `image`.
+enum { MSM_IMAGE_STD = 0, MSM_IMAGE_F = 1 };
 int msm_bases_build(zkmi_ctx* ctx, int group, const void* bases_dev, size_t n, const WinPlan& plan,
-                    zkmi_msm_bases** out);
+                    zkmi_msm_bases** out, int image = MSM_IMAGE_STD);
 // scalars batch-inner: element (row, b) at scalars[row * Bp + b]; row_idx (device, may be null)
 // maps base i to its scalar row.  out_xyzz: Bp accumulators.
 // scalars_f: the scalars are in the F domain (solver output) instead of gnark's image
@@ -386,9 +398,18 @@ int msm_bases_build(zkmi_ctx* ctx, int group, const void* bases_dev, size_t n, c
 // (comb plans) the sums over the chunk partials run there too (ordered after the accumulate launch
 // by an event; the partials of consecutive MSMs alternate between two buffers), so the main stream
 // holds nothing but the digit pass and the accumulate kernel.
+// Comb plans, which groups are uniform: row_varies (device, may be null) = msm_rows_vary's flags
+// of the rows of `scalars`, shared by every MSM that reads the same rows; dense = do not look,
+// every group varies (scalars with no structure, such as the quotient's).  With neither, msm_run
+// compares the rows of its own bases.
 int msm_run(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, const uint32_t* row_idx,
             size_t Bp, size_t batch, void* out_xyzz, bool scalars_f = false,
-            void* wsum_out = nullptr, hipStream_t finish_stream = nullptr);
+            void* wsum_out = nullptr, hipStream_t finish_stream = nullptr,
+            const uint8_t* row_varies = nullptr, bool dense = false);
+// flags[row] = 1 when row `row` of the batch-inner matrix differs between two of its first `batch`
+// lanes, else 0 (n_rows flags, device)
+int msm_rows_vary(zkmi_ctx* ctx, const Fr* rows, size_t n_rows, size_t Bp, size_t batch,
+                  uint8_t* flags);
 // Horner step of up to four deferred MSMs of one group (same plan) in one launch on `stream`
 int msm_horner_run(zkmi_ctx* ctx, hipStream_t stream, int count,
                    const zkmi_msm_bases* const* bases, void* const* wsums, void* const* outs,

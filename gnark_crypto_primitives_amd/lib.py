@@ -83,6 +83,8 @@ SYMBOLS = [
     ("zkmi_msm_bases_load", _I, [_P, _I, _P, _SZ, _I, C.POINTER(_P)]),
     ("zkmi_msm_bases_free", None, [_P, _P]),
     ("zkmi_msm_batch", _I, [_P, _P, _P, _SZ, _P]),
+    ("zkmi_msm_bases_load_image", _I, [_P, _I, _P, _SZ, _I, _I, C.POINTER(_P)]),
+    ("zkmi_msm_batch_rows", _I, [_P, _P, _P, _SZ, _P, _SZ, _I, _I, _P]),
     ("zkmi_comb_min_groups_per_chunk", C.c_uint32, []),
     ("zkmi_fixed_base_mul", _I, [_P, _I, _P, _P, _SZ, _P]),
     ("zkmi_pk_load", _I, [_P, C.POINTER(PkDesc), C.POINTER(_P)]),
@@ -248,6 +250,19 @@ class Context:
     def msm_batch(self, bases_h, scalars, batch, out):
         self._check(self.lib.zkmi_msm_batch(self.h, bases_h, _ptr(scalars), batch, _ptr(out)),
                     "zkmi_msm_batch")
+        return out
+
+    def msm_bases_load_image(self, group, bases, n, window_bits, image):
+        h = C.c_void_p()
+        self._check(self.lib.zkmi_msm_bases_load_image(self.h, group, _ptr(bases), n, window_bits,
+                                                       image, C.byref(h)),
+                    "zkmi_msm_bases_load_image")
+        return h
+
+    def msm_batch_rows(self, bases_h, scalars, n_rows, row_idx, batch, image, uniform, out):
+        self._check(self.lib.zkmi_msm_batch_rows(self.h, bases_h, _ptr(scalars), n_rows,
+                                                 _ptr(row_idx), batch, image, uniform, _ptr(out)),
+                    "zkmi_msm_batch_rows")
         return out
 
     def comb_min_groups_per_chunk(self):

@@ -117,6 +117,21 @@ void zkmi_msm_bases_free(zkmi_ctx* ctx, zkmi_msm_bases* b);
  *   scalars: batch x n fr elements (Montgomery), proof-major; out: batch affine points. */
 int zkmi_msm_batch(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const void* scalars, size_t batch,
                    void* out);
+/* The two calls above with the choices the prover makes inside spelled out (tests, tools).
+ *   image: the canonical image the scalars are in, 0 = x * 2^256 (Montgomery, as everywhere in this
+ *          header), 1 = x * 2^261 (the witness solver's).  A sign-pattern comb table is built native
+ *          to the image given at the load and reads such scalars as they are; scalars of the other
+ *          image cost one conversion pass.  Every combination gives the same points.
+ *   scalars: batch x n_rows fr elements, proof-major; base i takes row row_idx[i] (n entries, each
+ *          below n_rows; NULL: row i).
+ *   uniform: how comb plans find the groups whose scalars the whole batch shares: 0 = from the
+ *          rows of the bases, inside the MSM; 1 = from one pass over all n_rows rows before it;
+ *          2 = not at all (every group is summed per proof). */
+int zkmi_msm_bases_load_image(zkmi_ctx* ctx, int group, const void* bases, size_t n,
+                              int window_bits, int image, zkmi_msm_bases** out);
+int zkmi_msm_batch_rows(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const void* scalars,
+                        size_t n_rows, const uint32_t* row_idx, size_t batch, int image, int uniform,
+                        void* out);
 /* Comb tables: fewest groups with batch-varying scalars that are worth a chunk (a row of
  * accumulate blocks and a partial sum of its own) in one MSM launch. */
 uint32_t zkmi_comb_min_groups_per_chunk(void);
