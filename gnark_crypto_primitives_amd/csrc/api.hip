@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "zkmi_internal.h"
+#include "comb_plan.h"
 #include "ff29.h"
 #include "ec29.h"
 
@@ -686,7 +687,7 @@ int zkmi_msm_bases_load_image(zkmi_ctx* ctx, int group, const void* bases, size_
     if (n >= 64) {
       int k1, k2;
       bool s1, s2;
-      plan_comb_for_budget(group == 1 ? n : 0, group == 2 ? n : 0, 0.9 * usable, &k1, &k2, &s1, &s2);
+      comb_plan_equal(group == 1 ? n : 0, group == 2 ? n : 0, 0.9 * usable, &k1, &k2, &s1, &s2, true);
       const int k = group == 1 ? k1 : k2;
       if ((double)COMB_W / k < (double)plan.W) plan = plan_comb(k, group == 1 ? s1 : s2);
     }
@@ -863,8 +864,26 @@ static int wires_from_infinity(zkmi_ctx* ctx, const uint8_t* inf, uint32_t n_wir
 }
 
 int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
+  return zkmi_pk_load_planned(ctx, d, nullptr, out);
+}
+
+int zkmi_pk_load_planned(zkmi_ctx* ctx, const zkmi_pk_desc* d, const uint32_t* msm_window_bits,
+                         zkmi_pk** out) {
   ZK_HIP(hipSetDevice(ctx->device));
   if (!d || !out) return ZKMI_ERR_ARG;
+  if (msm_window_bits)
+    for (int i = 0; i < COMB_PLAN_MSMS; i++)
+      if (msm_window_bits[i] == 0 || !window_bits_ok((int)msm_window_bits[i])) {
+        ctx->err = "pk: msm_window_bits must be in [2,16], 100 + [4,16], 200 + [2,20] or 300 + [3,21]";
+        return ZKMI_ERR_ARG;
+      }
+  // the G1 window sums are finished together (zkmi_prove_collect_ex): all four stop at them, or none
+  if (msm_window_bits)
+    for (int i = 0; i < COMB_MSM_Z; i++)
+      if ((msm_window_bits[i] >= 100) != (msm_window_bits[COMB_MSM_Z] >= 100)) {
+        ctx->err = "pk: msm_window_bits of A, B1, K and Z must all be per-window plans or none";
+        return ZKMI_ERR_ARG;
+      }
   if (d->log_n < 1 || d->log_n > 28) {
     ctx->err = "pk: log_n out of range [1,28]";
     return ZKMI_ERR_ARG;
@@ -978,7 +997,8 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
     zkmi_pk_free(ctx, pk);
     return rc;
   }
-  // One window plan per group for the whole key.  Auto plans are sized against the free HBM minus
+  // One window plan per group for the whole key; comb plans then get a group size per MSM (below).
+  // Auto plans are sized against the free HBM minus
   // the working set of the largest batch the caller will prove (and the caller's own cap).
   const bool auto1 = d->window_bits_g1 == 0, auto2 = d->window_bits_g2 == 0;
   const size_t n1 = (size_t)d->n_a + d->n_b + n_kb + n_zb;
@@ -1002,19 +1022,24 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
   if (auto1 && sc1 && plan_shared(sc1).W < p1.W) p1 = plan_shared(sc1);
   if (auto2 && sc2 && plan_shared(sc2).W < p2.W) p2 = plan_shared(sc2);
   // comb tables (joint tables over k bases) when they need fewer additions per base still; small
-  // keys keep the layouts above (their MSMs are latency, not throughput)
+  // keys keep the layouts above (their MSMs are latency, not throughput).  Each MSM gets a group
+  // size of its own (comb_plan.h): the dense quotient MSM executes every group of every proof, the
+  // wire MSMs only the groups that vary over the batch, so Z takes more of the bytes.
+  WinPlan pm[COMB_PLAN_MSMS] = {p1, p1, p1, p1, p2};   // A, B1, K, Z, B2
   if (n1 >= 4096) {
-    int k1 = 0, k2 = 0;
-    bool s1 = true, s2 = true;
-    plan_comb_for_budget(auto1 ? n1 : 0, auto2 ? d->n_b : 0, 0.98 * usable, &k1, &k2, &s1, &s2,
-                         d->sparse_witness == 0);
-    if (auto1 && (double)COMB_W / k1 < (double)p1.W) p1 = plan_comb(k1, s1);
-    if (auto2 && (double)COMB_W / k2 < (double)p2.W) p2 = plan_comb(k2, s2);
+    const size_t nm[COMB_PLAN_MSMS] = {auto1 ? d->n_a : 0u, auto1 ? d->n_b : 0u, auto1 ? n_kb : 0u,
+                                       auto1 ? n_zb : 0u, auto2 ? d->n_b : 0u};
+    const CombPlan eq = comb_plan_equal5(nm, 0.98 * usable, d->sparse_witness == 0);
+    const CombPlan cp = comb_plan_search(nm, 0.98 * usable, d->sparse_witness == 0);
+    for (int i = 0; i < COMB_PLAN_MSMS; i++) {
+      const bool g2 = comb_msm_is_g2(i);
+      if ((g2 ? auto2 : auto1) && (double)COMB_W / eq.k[i] < (double)(g2 ? p2 : p1).W)
+        pm[i] = plan_comb(cp.k[i], cp.sg[i]);
+    }
   }
   // sparse_witness = 2: (almost) every wire is a bit.  The wire MSMs then execute one addition per
   // group (window 0) whatever the group size, so they get small subset-sum tables and the dense
   // quotient MSM (h . Z) gets the HBM: the widest table that fits, sign patterns allowed.
-  WinPlan p1z = p1;
   if (d->sparse_witness >= 2 && auto1 && auto2 && n1 >= 4096 && n_zb >= 4096) {
     const int kw = 12;
     const double wire_bytes =
@@ -1024,12 +1049,18 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
     if (wire_bytes < 0.5 * usable) {
       int kz = 0, k2 = 0;
       bool sz = true, s2 = true;
-      plan_comb_for_budget(n_zb, 0, 0.98 * usable - wire_bytes, &kz, &k2, &sz, &s2, true);
-      p1 = plan_comb(kw, false);
-      p2 = plan_comb(kw, false);
-      p1z = plan_comb(kz, sz);
+      comb_plan_equal(n_zb, 0, 0.98 * usable - wire_bytes, &kz, &k2, &sz, &s2, true);
+      for (int i = 0; i < COMB_PLAN_MSMS; i++) pm[i] = plan_comb(kw, false);
+      pm[COMB_MSM_Z] = plan_comb(kz, sz);
     }
   }
+  // an explicit plan per MSM (zkmi_pk_load_planned) replaces all of the above
+  bool relax[COMB_PLAN_MSMS] = {auto1, auto1, auto1, auto1, auto2};
+  if (msm_window_bits)
+    for (int i = 0; i < COMB_PLAN_MSMS; i++) {
+      pm[i] = plan_explicit((int)msm_window_bits[i]);
+      relax[i] = false;
+    }
   // The wire MSMs read the value file, which the solver leaves in the F image; the quotient MSM
   // reads h (or the coset evaluations of a folded key), which the NTT leaves in gnark's: sign-
   // pattern tables are built native to those, so that the digit pass reads both as they are.
@@ -1046,13 +1077,13 @@ int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk** out) {
   if ((rc = upload_u32(ctx, wa.data(), d->n_a, &pk->a_wire)) ||
       (rc = upload_u32(ctx, wb.data(), d->n_b, &pk->b_wire)) ||
       (rc = upload_u32(ctx, fold.folded ? fold.k_wire.data() : wk.data(), n_kb, &pk->k_wire)) ||
-      (rc = load(1, d->g1_a, d->n_a, p1, auto1, &pk->A, MSM_IMAGE_F)) ||
-      (rc = load(1, d->g1_b, d->n_b, p1, auto1, &pk->B1, MSM_IMAGE_F)) ||
-      (rc = load(1, fold.folded ? (const void*)fold.k.data() : d->g1_k, n_kb, p1, auto1, &pk->K,
-                 MSM_IMAGE_F)) ||
-      (rc = load(1, fold.folded ? (const void*)fold.e.data() : d->g1_z, n_zb, p1z, auto1, &pk->Z,
-                 MSM_IMAGE_STD)) ||
-      (rc = load(2, d->g2_b, d->n_b, p2, auto2, &pk->B2, MSM_IMAGE_F))) {
+      (rc = load(1, d->g1_a, d->n_a, pm[COMB_MSM_A], relax[COMB_MSM_A], &pk->A, MSM_IMAGE_F)) ||
+      (rc = load(1, d->g1_b, d->n_b, pm[COMB_MSM_B1], relax[COMB_MSM_B1], &pk->B1, MSM_IMAGE_F)) ||
+      (rc = load(1, fold.folded ? (const void*)fold.k.data() : d->g1_k, n_kb, pm[COMB_MSM_K],
+                 relax[COMB_MSM_K], &pk->K, MSM_IMAGE_F)) ||
+      (rc = load(1, fold.folded ? (const void*)fold.e.data() : d->g1_z, n_zb, pm[COMB_MSM_Z],
+                 relax[COMB_MSM_Z], &pk->Z, MSM_IMAGE_STD)) ||
+      (rc = load(2, d->g2_b, d->n_b, pm[COMB_MSM_B2], relax[COMB_MSM_B2], &pk->B2, MSM_IMAGE_F))) {
     zkmi_pk_free(ctx, pk);
     return rc;
   }
@@ -1087,6 +1118,16 @@ int zkmi_pk_info(const zkmi_pk* pk, uint64_t* info) {
   info[7] = pk->B2->plan.shared;
   info[8] = pk->Z->plan.comb;
   info[9] = pk->B2->plan.comb;
+  return ZKMI_OK;
+}
+
+int zkmi_pk_msm_plan(const zkmi_pk* pk, uint32_t* plan) {
+  if (!pk || !plan) return ZKMI_ERR_ARG;
+  const zkmi_msm_bases* ms[COMB_PLAN_MSMS] = {pk->A, pk->B1, pk->K, pk->Z, pk->B2};
+  for (int i = 0; i < COMB_PLAN_MSMS; i++) {
+    plan[i] = ms[i]->plan.comb;
+    plan[COMB_PLAN_MSMS + i] = ms[i]->plan.comb_signed;
+  }
   return ZKMI_OK;
 }
 
@@ -1393,11 +1434,14 @@ int zkmi_prove_collect_ex(zkmi_ctx* ctx, void* proofs_out, int32_t* status_out,
     void* ws[4] = {v.w1[0], v.w1[1], v.w1[2], v.w1[3]};
     void* os[4] = {v.sA, v.sB1, v.sK, v.sZ};
     const zkmi_msm_bases* ms[4] = {pk->A, pk->B1, pk->K, pk->Z};
-    bool same = true;   // an out-of-memory relaxation may have narrowed one table
+    // One launch for the four when their window sums combine alike.  Comb plans: 254 one-bit
+    // windows whatever the group size, so only the table kind has to agree (the correction window of
+    // sign-pattern tables; stotal is per MSM).  Shared tables: the same window widths.
+    bool same = true;
     for (int i = 0; i < 3; i++)
-      same = same && ms[i]->plan.bits[0] == pk->Z->plan.bits[0] &&
-             ms[i]->plan.comb == pk->Z->plan.comb &&
-             ms[i]->plan.comb_signed == pk->Z->plan.comb_signed;
+      same = same && (ms[i]->plan.comb != 0) == (pk->Z->plan.comb != 0) &&
+             ms[i]->plan.comb_signed == pk->Z->plan.comb_signed &&
+             (pk->Z->plan.comb || (ms[i]->plan.shared && ms[i]->plan.bits[0] == pk->Z->plan.bits[0]));
     if (same) {
       if ((rc = msm_horner_run(ctx, q3, 4, ms, ws, os, Bp))) return rc;
     } else {

@@ -31,6 +31,7 @@
 // coordinate field and go on in the templates of msm_impl.h.  msm_g2.hip is the second translation
 // unit of the MSM.
 #include "msm_impl.h"
+#include "comb_plan.h"
 
 namespace zk {
 
@@ -86,38 +87,11 @@ WinPlan plan_comb(int k, bool signed_tables) {
   p.per_base = 0;
   return p;
 }
-// Comb plan of a key: group sizes (k1, k2) and table kinds minimising the estimated accumulate
-// time among the plans whose tables fit `usable_bytes`.  Sign-pattern tables hold 2^(k-1) entries
-// per group and need 255 windows, subset-sum tables 2^k entries and 254 windows.  Relative cost of
-// one mixed addition, measured on MI355X (Arbo-160 key, ns per (group, window) at 1024 proofs):
-// G1 subset-sum 61.1, G1 sign-pattern 62.8 (the per-lane negation), G2 subset-sum 171.6, G2
-// sign-pattern 178.5 (198.8 while the G2 accumulator's zz / zzz lived in scratch: the extra live sign
-// spilled; re-measured with them in LDS at the end of round 3: 60.5 ms against 58.0 ms per MSM at
-// k = 19, and 57.1 ms with the k = 20 the same HBM affords).
+// Comb plan with one group size per group of the key (comb_plan.h, where the prices of the
+// additions are; zkmi_pk_load plans each MSM on its own with comb_plan_search)
 void plan_comb_for_budget(size_t n1, size_t n2, double usable_bytes, int* k1, int* k2, bool* sg1,
                           bool* sg2, bool allow_signed) {
-  // allow_signed = false: witnesses of bits / small integers (zkmi_pk_desc.sparse_witness): only
-  // subset-sum tables skip their zero digits (measured on the Keccak address circuit: 172 ms with
-  // them, 280 ms with sign patterns, for 5 % more additions on paper)
-  double best = 1e300;
-  *k1 = *k2 = 8;
-  *sg1 = *sg2 = allow_signed;
-  for (int s1 = 0; s1 < (allow_signed ? 2 : 1); s1++)
-    for (int s2 = 0; s2 < (allow_signed ? 2 : 1); s2++)
-      for (int a = 8; a <= (s1 ? 21 : 20); a++)
-        for (int b = 8; b <= (s2 ? 21 : 20); b++) {
-          const double g1 = (double)((n1 + a - 1) / a), g2 = (double)((n2 + b - 1) / b);
-          const double bytes = g1 * (double)(1u << (a - s1)) * 64.0 + g2 * (double)(1u << (b - s2)) * 128.0;
-          if (bytes > usable_bytes) continue;
-          const double cost = g1 * (s1 ? 255 * 62.8 : 254 * 61.1) + g2 * (s2 ? 255 * 178.5 : 254 * 171.6);
-          if (cost < best) {
-            best = cost;
-            *k1 = a;
-            *k2 = b;
-            *sg1 = s1 != 0;
-            *sg2 = s2 != 0;
-          }
-        }
+  comb_plan_equal(n1, n2, usable_bytes, k1, k2, sg1, sg2, allow_signed);
 }
 // Widths of the shared tables of a key: the (c1, c2) that minimises n1 * W(c1) + 3 * n2 * W(c2)
 // (a G2 mixed addition costs about three G1 ones) among those whose tables fit `usable_bytes`.

@@ -218,7 +218,8 @@ class Prover:
     def __init__(self, ctx: _lib.Context, cc: CompiledCircuit, pk: ProvingKey,
                  window_bits_g1: int = 0, window_bits_g2: int = 0, *, max_batch: int = 0,
                  table_budget_bytes: int = 0, msm_chunk_factor: int = 0,
-                 gnark_key_layout: bool = False, sparse_witness=None, fold_quotient=None):
+                 gnark_key_layout: bool = False, sparse_witness=None, fold_quotient=None,
+                 msm_window_bits=None):
         """max_batch / table_budget_bytes / msm_chunk_factor: zkmi_pk_desc plan fields
         (0 = default).  sparse_witness: zkmi_pk_desc.sparse_witness; None = from the circuit (more
         than half of its wires are known booleans: Keccak, bit decompositions).  gnark_key_layout: describe the key the way
@@ -226,7 +227,8 @@ class Prover:
         arrays; the loaded key is the same.  fold_quotient: hand the circuit's O matrix to the key
         load (zkmi_pk_desc.fold_r1cs) so that the quotient MSM takes evaluations; None = when the
         key has no commitments.  The library leaves keys with commitments and domains below 2^8
-        unfolded either way (``folded`` tells)."""
+        unfolded either way (``folded`` tells).  msm_window_bits: explicit window_bits of the A, B1,
+        K, Z and B2 tables (zkmi_pk_load_planned) in the place of window_bits_g1 / g2."""
         self.ctx, self.cc, self.pk = ctx, cc, pk
         self.n_inputs = cc.n_inputs
         self._consts = to_mont_array(cc.consts) if cc.consts else np.zeros((0, 4), np.uint64)
@@ -278,7 +280,7 @@ class Prover:
                          self.n_commitments,
                          C.addressof(cdescs) if self.n_commitments else None,
                          C.addressof(fold) if fold is not None else None)
-        self.pk_h = ctx.pk_load(pd)
+        self.pk_h = ctx.pk_load(pd, msm_window_bits)
         self.folded = ctx.pk_folded(self.pk_h)
 
     def _r1cs_desc(self):

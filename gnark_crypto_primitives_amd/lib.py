@@ -89,7 +89,9 @@ SYMBOLS = [
     ("zkmi_fixed_base_mul", _I, [_P, _I, _P, _P, _SZ, _P]),
     ("zkmi_pk_load", _I, [_P, C.POINTER(PkDesc), C.POINTER(_P)]),
     ("zkmi_pk_free", None, [_P, _P]),
+    ("zkmi_pk_load_planned", _I, [_P, C.POINTER(PkDesc), C.POINTER(C.c_uint32), C.POINTER(_P)]),
     ("zkmi_pk_info", _I, [_P, C.POINTER(C.c_uint64)]),
+    ("zkmi_pk_msm_plan", _I, [_P, C.POINTER(C.c_uint32)]),
     ("zkmi_pk_folded", _I, [_P]),
     ("zkmi_cs_load", _I, [_P, C.POINTER(CsDesc), C.POINTER(_P)]),
     ("zkmi_cs_free", None, [_P, _P]),
@@ -274,17 +276,30 @@ class Context:
         return out
 
     # ---- key / system handles
-    def pk_load(self, desc: PkDesc):
+    def pk_load(self, desc: PkDesc, msm_window_bits=None):
+        """msm_window_bits: window_bits of A, B1, K, Z, B2 (zkmi_pk_load_planned); None = the
+        descriptor's window_bits_g1 / g2 or the auto plan"""
         h = C.c_void_p()
-        self._check(self.lib.zkmi_pk_load(self.h, C.byref(desc), C.byref(h)), "zkmi_pk_load")
+        if msm_window_bits is None:
+            self._check(self.lib.zkmi_pk_load(self.h, C.byref(desc), C.byref(h)), "zkmi_pk_load")
+        else:
+            wb = (C.c_uint32 * 5)(*msm_window_bits)
+            self._check(self.lib.zkmi_pk_load_planned(self.h, C.byref(desc), wb, C.byref(h)),
+                        "zkmi_pk_load_planned")
         return h
 
     def pk_info(self, h):
         arr = (C.c_uint64 * 10)()
         self._check(self.lib.zkmi_pk_info(h, arr), "zkmi_pk_info")
-        return dict(zip(("g1_windows", "g1_entries_per_base", "g2_windows", "g2_entries_per_base",
+        info = dict(zip(("g1_windows", "g1_entries_per_base", "g2_windows", "g2_entries_per_base",
                          "g1_table_bytes", "g2_table_bytes", "g1_shared", "g2_shared",
                          "g1_comb_k", "g2_comb_k"), [int(x) for x in arr]))
+        # g1_* describe the quotient MSM's tables (Z); the comb plan of every MSM:
+        plan = (C.c_uint32 * 10)()
+        self._check(self.lib.zkmi_pk_msm_plan(h, plan), "zkmi_pk_msm_plan")
+        info["msm_comb_k"] = dict(zip(("A", "B1", "K", "Z", "B2"), [int(x) for x in plan[:5]]))
+        info["msm_comb_signed"] = dict(zip(("A", "B1", "K", "Z", "B2"), [int(x) for x in plan[5:]]))
+        return info
 
     def pk_folded(self, h) -> bool:
         return bool(self.lib.zkmi_pk_folded(h))

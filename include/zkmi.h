@@ -238,12 +238,24 @@ typedef struct {
 /* Copies the key to the device and builds the MSM window tables; host buffers may be freed
  * afterwards.  One-off per circuit (gnark's icicle backend does the same lazily). */
 int zkmi_pk_load(zkmi_ctx* ctx, const zkmi_pk_desc* desc, zkmi_pk** out);
+/* The same with an explicit table plan for each of the key's five MSMs: msm_window_bits[5] = the
+ * window_bits (as zkmi_msm_bases_load; 0 is not accepted) of A, B1, K, Z and B2, in this order, in
+ * the place of window_bits_g1 / window_bits_g2 and of the auto plan.  NULL = zkmi_pk_load.  The auto
+ * plan of a key of 4096 or more G1 bases gives each MSM a comb group size of its own: the quotient
+ * MSM (Z), whose scalars are dense, a wider table than the wire MSMs, which execute only the
+ * groups that vary over the batch (zkmi_pk_msm_plan tells what was chosen). */
+int zkmi_pk_load_planned(zkmi_ctx* ctx, const zkmi_pk_desc* desc, const uint32_t* msm_window_bits,
+                         zkmi_pk** out);
 void zkmi_pk_free(zkmi_ctx* ctx, zkmi_pk* pk);
 /* Window plan chosen for the key: info[0] = windows per G1 scalar, [1] = table entries per G1
  * base, [2] = windows per G2 scalar, [3] = table entries per G2 base, [4] = G1 table bytes (all
  * four MSMs), [5] = G2 table bytes, [6] / [7] = 1 when the G1 / G2 tables are shared-table plans,
  * [8] / [9] = group size k of the G1 / G2 comb tables (0 otherwise; then [0] / [2] = 254). */
 int zkmi_pk_info(const zkmi_pk* pk, uint64_t* info /* 10 */);
+/* Comb plan per MSM: plan[0..4] = group size k of the comb tables of A, B1, K, Z and B2 (0: not a
+ * comb plan), plan[5..9] = 1 when they are sign-pattern tables.  zkmi_pk_info's [0], [1], [6] and
+ * [8] describe Z, its [2], [3], [7] and [9] B2. */
+int zkmi_pk_msm_plan(const zkmi_pk* pk, uint32_t* plan /* 10 */);
 /* 1 when the key was loaded with its quotient bases in evaluation form (fold_r1cs), else 0. */
 int zkmi_pk_folded(const zkmi_pk* pk);
 
