@@ -31,6 +31,7 @@ struct zkmi_r1cs_solver {
   uint32_t n_wires = 0, n_constraints = 0, n_inputs = 0, n_instr = 0, S = 1;
   uint32_t n_records = 0;             // what the kernel walks: n_instr, or more with lookup hints
   bool ext = false;                   // the plan holds a record kind of ZKMI_HINTS_STD
+  bool emul = false;                  // the plan holds emulated-product records (ZKMI_HINTS_EMULATED)
   std::vector<R1csCommit> commits;    // host: the commitment hints, the launches' boundaries
   uint32_t longest = 0, n_inversions = 0;
   uint64_t n_terms = 0;
@@ -75,13 +76,18 @@ __device__ __forceinline__ Fr sum_sublanes(Fr v) {
 // of an NBits hint: fetched again), so no instruction waits for its predecessor's store.
 // A launch runs the records [begin, end): records and terms are contiguous and end in the slack the
 // plan appends, so the fetches start at records[begin] and run ahead of `end` like anywhere else.
-// EXT = the plan holds record kinds of ZKMI_HINTS_STD (limbs, byte operations, lookup
-// multiplicities); plans without one run the EXT = false instance, which holds none of their code.
+// EXT = 1: the plan holds record kinds of ZKMI_HINTS_STD (limbs, byte operations, lookup
+// multiplicities); plans without one run the EXT = 0 instance, which holds none of their code.
+// EXT = 2: the plan also holds emulated-product records (ZKMI_HINTS_EMULATED); the other two
+// instances hold none of that code either.  The steps of such a hint leave every sub-lane of a
+// proof the field images of all operand limbs (L below, live from the first step to the closing
+// record); the closing record is r1cs_emul_finish (r1cs_plan.h), run by every sub-lane alike, with
+// the output stores split over the sub-lanes.
 // A lookup hint counts with an atomic add on the low word of the counter's wire slot and reads back
 // with the same scope, as the CLS_HIST branch of solve_vliw_kernel (solve.hip) does: the sub-lanes of
 // a proof share the counters.
 // All counts and indices come from a plan that r1cs_plan_build has checked.
-template <int S, bool EXT>
+template <int S, int EXT>
 __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict__ recs,
                                                         const uint2* __restrict__ terms,
                                                         const Fr* __restrict__ coeffs,
@@ -102,6 +108,11 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
   uint2 t0 = tp[0], t1 = tp[S], t2 = tp[2 * S];
   Fr x0 = bi_ld(w, t0.x & R1CS_IDX_MASK, p, Bp), x1 = bi_ld(w, t1.x & R1CS_IDX_MASK, p, Bp);
   Fr k0 = coeffs[t0.y & R1CS_IDX_MASK], k1 = coeffs[t1.y & R1CS_IDX_MASK];
+  Fr L[8];   // EXT = 2: the operand limbs of the emulated product in work
+  if constexpr (EXT == 2) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) L[q] = Fr::zero();
+  }
   for (uint32_t i = begin; i < end; i++) {
     const uint32_t kind = __builtin_amdgcn_readfirstlane(r0.x);
     const uint32_t target = __builtin_amdgcn_readfirstlane(r0.y);
@@ -109,6 +120,8 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
     const uint32_t unit_rows = __builtin_amdgcn_readfirstlane(r1.z);
     const uint32_t k = __builtin_amdgcn_readfirstlane(r1.w);
     const Fr kinv = coeffs[__builtin_amdgcn_readfirstlane(r0.w)];
+    // RK_EMUL_END: where the modulus sits (kinv is the modulus itself, its limbs' images follow)
+    const uint32_t mod_at = EXT == 2 ? (uint32_t)__builtin_amdgcn_readfirstlane(r0.w) : 0u;
     const uint32_t par = EXT ? __builtin_amdgcn_readfirstlane(r0.z) : 0u;   // width, operation, size
     Fr sa = Fr::zero(), sb = Fr::zero(), sc = Fr::zero();
     // v joins the sum its tag names; a padding term joins none
@@ -134,12 +147,36 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
     // the next instruction's record, before this one's stores
     r0 = recs[2 * (size_t)(i + 1)];
     r1 = recs[2 * (size_t)(i + 1) + 1];
-    if (S > 1 && !(EXT && kind == RK_COUNT_Q)) {   // a query is its sub-lane's own sum
+    // a query is its sub-lane's own sum, and so is an operand limb of an emulated product
+    if (S > 1 && !(EXT && kind == RK_COUNT_Q) && !(EXT == 2 && kind == RK_EMUL_STEP)) {
       sa = sum_sublanes<S>(sa);
       sb = sum_sublanes<S>(sb);
       sc = sum_sublanes<S>(sc);
     }
-    if (EXT && kind >= RK_LIMBS) {
+    if (EXT == 2 && kind >= RK_EMUL_STEP) {
+      if constexpr (EXT == 2) {
+        if (kind == RK_EMUL_STEP) {
+          // limbs target .. target + k - 1, one per sub-lane: every sub-lane fetches them all from
+          // their owners in the same proof
+#pragma unroll
+          for (int q = 0; q < 8; q++)
+            if ((uint32_t)q >= target && (uint32_t)q < target + k) {
+              const int owner = (int)((uint32_t)q - target) * PPW + (int)(threadIdx.x % PPW);
+#pragma unroll
+              for (int t = 0; t < 8; t++) L[q].v[t] = __shfl(sa.v[t], owner, 64);
+            }
+        } else {
+          r1cs_emul_finish(L, kinv, coeffs + mod_at + 1, par,
+                           [&](uint32_t o, const Fr& v) {
+                             if ((o & (S - 1)) == sl) bi_st(w, outs[target + o], p, Bp, v);
+                           });
+          // the wire values fetched ahead may be among the wires stored: fetch them again behind the stores
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+          x0 = bi_ld(w, t0.x & R1CS_IDX_MASK, p, Bp);
+          x1 = bi_ld(w, t1.x & R1CS_IDX_MASK, p, Bp);
+        }
+      }
+    } else if (EXT && kind >= RK_LIMBS) {
       if (kind == RK_BYTEOP) {
         const uint32_t u = from_mont(sa).v[0], v = from_mont(sb).v[0];
         const Fr xs = r1cs_small(par == 1 ? u ^ v : u & v);
@@ -248,7 +285,7 @@ __global__ void r1cs_solve_init_kernel(Fr* w, int32_t* status, size_t Bp) {
 template <int S>
 static void launch_r1cs_solve(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, Fr* w, Fr* a, Fr* b, Fr* c,
                               int32_t* status, size_t Bp, uint32_t begin, uint32_t end) {
-  const auto kernel = s->ext ? r1cs_solve_kernel<S, true> : r1cs_solve_kernel<S, false>;
+  const auto kernel = s->emul ? r1cs_solve_kernel<S, 2> : s->ext ? r1cs_solve_kernel<S, 1> : r1cs_solve_kernel<S, 0>;
   hipLaunchKernelGGL(kernel, dim3((unsigned)(Bp * S / 64)), dim3(64), 0, ctx->stream, s->records,
                      s->terms, s->coeffs, s->outs, w, a, b, c, status, Bp, begin, end);
 }
@@ -385,6 +422,7 @@ static int solver_load(zkmi_ctx* ctx, const zkmi_r1cs* m, const zkmi_r1cs_solver
   s->n_instr = plan.n_instr;
   s->n_records = (uint32_t)plan.records.size() - 1;
   s->ext = plan.ext;
+  s->emul = plan.emul;
   s->commits = std::move(plan.commits);
   s->S = plan.S;
   s->longest = plan.longest;

@@ -311,12 +311,12 @@ class Prover:
         gnark ccs describes it -- L, R, O, the instruction order and the hint table.  The frontend's
         solve wires and its witness program are deliberately left out: the library finds every
         constraint's unknown itself.  lanes_per_proof: 0 = auto, or a power of two, 1 .. 64.
-        hints: "basic" (InvZero, NBits) or "std" (additionally limbs, lookup multiplicities, byte
-        operations and commitments: ZKMI_HINTS_STD).  A solver loaded with other arguments is
-        replaced."""
-        sets = {"basic": _lib.HINTS_BASIC, "std": _lib.HINTS_STD}
+        hints: "basic" (InvZero, NBits), "std" (additionally limbs, lookup multiplicities, byte
+        operations and commitments: ZKMI_HINTS_STD) or "emulated" (additionally the product hint of
+        std/math/emulated: ZKMI_HINTS_EMULATED).  A solver loaded with other arguments is replaced."""
+        sets = {"basic": _lib.HINTS_BASIC, "std": _lib.HINTS_STD, "emulated": _lib.HINTS_EMULATED}
         if hints not in sets:
-            raise ValueError('hints must be "basic" or "std"')
+            raise ValueError('hints must be "basic", "std" or "emulated"')
         if getattr(self, "r1cs_solver_h", None):
             if (lanes_per_proof, hints) == self._r1cs_solver_args:
                 return self.r1cs_solver_h

@@ -62,7 +62,7 @@ class R1csSolverDesc(C.Structure):
                 ("lanes_per_proof", C.c_uint32), ("hint_set", C.c_uint32)]
 
 
-HINTS_BASIC, HINTS_STD = 0, 1      # enum zkmi_hint_set
+HINTS_BASIC, HINTS_STD, HINTS_EMULATED = 0, 1, 3      # enum zkmi_hint_set (2 alone is not a set)
 
 
 # every symbol include/zkmi.h declares: (name, restype, argtypes)

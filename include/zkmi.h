@@ -391,8 +391,9 @@ int zkmi_prove_witness_batch(zkmi_ctx* ctx, const zkmi_pk* pk, const void* wires
 enum zkmi_hint_kind {
   ZKMI_HINT_INVZERO = 1, /* solver.InvZeroHint: one input x, one output 1/x, or 0 for x = 0 */
   ZKMI_HINT_NBITS = 2,   /* bits.NBits: one input, output i = bit i of its canonical value */
-  /* The kinds below are accepted under hint_set = ZKMI_HINTS_STD only.  Their first input
-   * expression is a constant parameter p0: terms on wire 0 (ONE) alone, evaluated at load time. */
+  /* The kinds below are accepted under hint_set = ZKMI_HINTS_STD and ZKMI_HINTS_EMULATED only.
+   * Their first input expression is a constant parameter p0: terms on wire 0 (ONE) alone, evaluated
+   * at load time. */
   ZKMI_HINT_LIMBS = 3,   /* p0 = width (1 .. 64), one value expression; output j = bits
                             [j width, (j + 1) width) of its canonical value, bits from 256 on are 0 */
   ZKMI_HINT_COUNT = 4,   /* p0 = table size = number of outputs; every further input is a query;
@@ -402,14 +403,31 @@ enum zkmi_hint_kind {
                             one output: the commitment wire.  Every operand is one solved wire with
                             coefficient 1.  A phase boundary of zkmi_prove_r1cs_submit, which needs the
                             key's commitment keys; refused by zkmi_r1cs_solve_batch */
-  ZKMI_HINT_BYTEOP = 6   /* p0 = 1 XOR | 2 AND, two expressions, one output: the operation on the low
+  ZKMI_HINT_BYTEOP = 6,  /* p0 = 1 XOR | 2 AND, two expressions, one output: the operation on the low
                             32 bits of their canonical values */
+  /* Accepted under hint_set = ZKMI_HINTS_EMULATED only: the product hint of std/math/emulated
+   * [UPSTREAM-RECALL].  p0 = na | nb << 8 | nk << 16, then na limb expressions of a, nb of b and four
+   * of the modulus p: 1 + na + nb + 4 inputs.  a = sum a_i 2^(64 i), where a limb may exceed 64 bits
+   * (lazy additions); b likewise.  The four modulus expressions are constants like p0 (an empty
+   * expression is 0), each below 2^64.  Outputs, in order: nk 64-bit limbs of floor(a b / p), four
+   * 64-bit limbs of a b mod p, then ncols - 1 carries, ncols = max(na + nb - 1, nk + 3): as field
+   * elements, c_j = (sum_i a_i b_(j-i) - r_j - sum_i k_i p_(j-i) + c_(j-1)) 2^-64.
+   * Limits: 1 <= na, nb <= 4, 1 <= nk <= 8, 2^224 <= p < 2^256 (checked at load time).  The
+   * caller's circuit keeps a, b < 2^384 and the quotient below 2^(64 nk): the integers are held in
+   * twelve 32-bit words per operand, and beyond that the quotient and remainder outputs are
+   * unspecified -- never a fault. */
+  ZKMI_HINT_EMULMUL = 7
 };
-/* The numbers are those of this repository's frontend.  Kind 7 (emulated product) and unknown kinds
- * are refused by name at load time under either hint set. */
+/* The numbers are those of this repository's frontend; the parity of the hints' names and operand
+ * order with gnark's own is not pinned.  Unknown kinds are refused by name at load time under every
+ * hint set, kind 7 under ZKMI_HINTS_BASIC and ZKMI_HINTS_STD. */
 enum zkmi_hint_set {
   ZKMI_HINTS_BASIC = 0, /* InvZero and NBits; every other kind is refused by name at load time */
-  ZKMI_HINTS_STD = 1    /* additionally limbs, lookup multiplicities, commitment, byte operations */
+  ZKMI_HINTS_STD = 1,   /* additionally limbs, lookup multiplicities, commitment, byte operations */
+  /* Read the field as bits: 1 = the kinds of ZKMI_HINTS_STD, 2 = the emulated product.  Every
+   * emulated circuit range-checks its limbs through the std kinds, so 2 alone is not offered and is
+   * refused. */
+  ZKMI_HINTS_EMULATED = 3 /* the kinds of ZKMI_HINTS_STD and the emulated product (kind 7) */
 };
 typedef struct {
   uint32_t n_public;  /* public wires including ONE */
@@ -453,8 +471,8 @@ int zkmi_r1cs_solve_batch(zkmi_ctx* ctx, const zkmi_r1cs_solver* solver, const v
                           size_t batch, void* wires_out, void* abc_out, int32_t* status_out);
 /* Stage 1 of a prove from inputs; the matching zkmi_prove_collect returns the proofs.  Pipelines
  * exactly like zkmi_prove_submit (two batches in flight, same streams, same HBM plan).  A key with
- * commitments needs a solver loaded with ZKMI_HINTS_STD whose commitment hints match the key's
- * commitments one by one (commitment wire, hashed and private wires, in order): the solve stops at
+ * commitments needs a solver loaded with ZKMI_HINTS_STD or ZKMI_HINTS_EMULATED whose commitment
+ * hints match the key's commitments one by one (commitment wire, hashed and private wires, in order): the solve stops at
  * each, the commitment is formed and hashed into its wire, and zkmi_prove_collect_ex returns
  * commitments and proof of knowledge.  Every mismatch is refused before anything is queued. */
 int zkmi_prove_r1cs_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_r1cs_solver* solver,

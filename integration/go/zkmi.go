@@ -26,7 +26,8 @@
 // solves (zkmi_prove_r1cs_submit; tests/test_gpu_r1cs_solver.py and tests/test_gpu_r1cs_hints.py
 // drive that sequence).  Hints solver.InvZeroHint and bits.NBits; with LoadSolver(..., std = true)
 // also the limb, lookup-multiplicity, byte-operation and commitment hints, so keys with commitments
-// go through it as well.  The emulated-product hint and every other hint is refused.
+// go through it as well; with LoadSolverWith(..., HintsEmulated) also the product hint of
+// std/math/emulated (tests/test_gpu_r1cs_emul.py).  Every other hint is refused.
 package zkmi
 
 /*
@@ -245,6 +246,10 @@ type Solver struct {
 // unpinned].  The library's contract for them (include/zkmi.h: a constant parameter first, then the
 // value expressions) is the one of this repository's frontend and of the C oracle; parity of this
 // table and of the operand order with gnark's own hints is not pinned by any test here.
+// The last entry is the product hint of std/math/emulated (ZKMI_HINTS_EMULATED) [UPSTREAM-RECALL:
+// its name, its parameter packing (na | nb << 8 | nk << 16 first, the modulus limbs last) and its
+// output order (quotient, remainder, carries) are those of this repository's frontend, unpinned
+// against gnark's own mulHint].
 var hintKinds = map[string]uint32{
 	"github.com/consensys/gnark/constraint/solver.InvZeroHint":                    C.ZKMI_HINT_INVZERO,
 	"github.com/consensys/gnark/std/math/bits.NBits":                              C.ZKMI_HINT_NBITS,
@@ -253,7 +258,17 @@ var hintKinds = map[string]uint32{
 	"github.com/consensys/gnark/frontend/cs/r1cs.bsb22CommitmentComputePlaceholder": C.ZKMI_HINT_COMMIT, // [UPSTREAM-RECALL]
 	"github.com/consensys/gnark/std/math/uints.xorHint":                           C.ZKMI_HINT_BYTEOP,  // [UPSTREAM-RECALL]
 	"github.com/consensys/gnark/std/math/uints.andHint":                           C.ZKMI_HINT_BYTEOP,  // [UPSTREAM-RECALL]
+	"github.com/consensys/gnark/std/math/emulated.mulHint":                        C.ZKMI_HINT_EMULMUL, // [UPSTREAM-RECALL]
 }
+
+// HintSet names the hint kinds a solver accepts (enum zkmi_hint_set).
+type HintSet uint32
+
+const (
+	HintsBasic    HintSet = C.ZKMI_HINTS_BASIC    // InvZero, NBits
+	HintsStd      HintSet = C.ZKMI_HINTS_STD      // and limbs, lookup multiplicities, byte operations, commitments
+	HintsEmulated HintSet = C.ZKMI_HINTS_EMULATED // and the product hint of std/math/emulated [UPSTREAM-RECALL]
+)
 
 // LoadSolver walks ccs.Instructions in order [UPSTREAM-RECALL: constraint.System{Instructions,
 // Blueprints}, PackedInstruction.Unpack, BlueprintHint.DecompressHint, HintMapping{HintID, Inputs,
@@ -264,6 +279,15 @@ var hintKinds = map[string]uint32{
 // commitments); without it the description is the basic one and those kinds are refused by name.
 // r1cs is the handle of LoadR1CS for the same ccs.
 func (d *Device) LoadSolver(ccs *cs_bn254.R1CS, r1cs *R1CS, lanesPerProof int, std bool) (*Solver, error) {
+	if std {
+		return d.LoadSolverWith(ccs, r1cs, lanesPerProof, HintsStd)
+	}
+	return d.LoadSolverWith(ccs, r1cs, lanesPerProof, HintsBasic)
+}
+
+// LoadSolverWith is LoadSolver with the hint set named: HintsEmulated for a circuit over an
+// emulated field (std/math/emulated), whose product hints are refused by name under the other two.
+func (d *Device) LoadSolverWith(ccs *cs_bn254.R1CS, r1cs *R1CS, lanesPerProof int, hints HintSet) (*Solver, error) {
 	names := make(map[solver.HintID]string)
 	for id, name := range ccs.MHintsDependencies {
 		names[id] = name
@@ -319,9 +343,7 @@ func (d *Device) LoadSolver(ccs *cs_bn254.R1CS, r1cs *R1CS, lanesPerProof int, s
 		desc.hint_terms = (*C.zkmi_term)(unsafe.Pointer(&terms[0]))
 	}
 	desc.lanes_per_proof = C.uint32_t(lanesPerProof) // 0 = auto
-	if std {
-		desc.hint_set = C.ZKMI_HINTS_STD // calloc left ZKMI_HINTS_BASIC
-	}
+	desc.hint_set = C.uint32_t(hints) // calloc left ZKMI_HINTS_BASIC
 	d.mu.Lock()
 	defer d.mu.Unlock()
 	var h *C.zkmi_r1cs_solver

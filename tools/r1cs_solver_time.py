@@ -6,8 +6,11 @@ line.  Workloads:
                   siblings, through the basic solver
   address-commit  the address circuit with its commitment-backed range checks (2^18 domain, 144
                   committed wires) x 64 proofs, through the solver loaded with hints="std"
+  emulated-poseidon  EmulatedPoseidonCircuit (2^17 domain, about 8 * 10^2 emulated products per
+                  proof) x 64 proofs -- the batch size of its GPU test, filled with that test's
+                  satisfied assignments -- through the solver loaded with hints="emulated"
 
-    python tools/r1cs_solver_time.py [--workload arbo160|address-commit] [--out FILE]
+    python tools/r1cs_solver_time.py [--workload arbo160|address-commit|emulated-poseidon] [--out FILE]
 
 Three GPU steps, each a child process of its own under its own time limit; the first step that fails
 ends the run (nothing more is started on the GPU):
@@ -15,7 +18,7 @@ ends the run (nothing more is started on the GPU):
                copied back: the gnark-shaped solver at the automatic lane count and at 8, 16, 32
                lanes per proof, then the frontend program.  Host clock around calls that end in a
                stream synchronise; one warm-up call, then the median and the least of five.
-               address-commit: a solve alone cannot supply the commitment, so the figure is the
+               address-commit, emulated-poseidon: a solve alone cannot supply the commitment, so the figure is the
                stage-1 device time (zkmi_last_timings [0]: solve launches, commitment MSM and hash)
                of submit_r1cs + collect, and of submit + collect, one batch at a time.
   pipe-program pipelined proofs/s of submit + collect over --steps batches (two in flight)
@@ -38,6 +41,8 @@ LEVELS, POPULATED, BATCH, DISTINCT = 160, 10, 1024, 64
 ADDRESS_BATCH = 64
 WORKLOAD = "arbo160"
 STEP_LIMIT_S = {"solve": 240, "pipe-program": 240, "pipe-r1cs": 300}
+# the workloads with a commitment: the hint set their solver is loaded with
+COMMITTED = {"address-commit": "std", "emulated-poseidon": "emulated"}
 
 
 def _setup_address(need_key):
@@ -49,13 +54,21 @@ def _setup_address(need_key):
     from gnark_crypto_primitives_amd.std.emulated import limbs_of
     from oracle import pyref
     ctx = lib.Context(0)
-    cc = compile_circuit(circuits.AddressCircuitCommit(), 16)
-    rng = random.Random(56)
-    distinct = []
-    for _ in range(4):
-        pub = pyref.secp256k1_mul(rng.randrange(1, pyref.SECP_N))
-        distinct.append(to_mont_array(cc.assignment_vector(
-            {"Address": pyref.eth_address(pub), "X": limbs_of(pub[0]), "Y": limbs_of(pub[1])})))
+    if WORKLOAD == "emulated-poseidon":
+        cc = compile_circuit(circuits.EmulatedPoseidonCircuit(), 16)
+        rng = random.Random(8)
+        mk = circuits.EmulatedPoseidonCircuit.assignment
+        distinct = [to_mont_array(cc.assignment_vector(a)) for a in
+                    (mk((1, 2, 3)), mk((0, 0, 0)), mk((groth16.R - 1, groth16.R - 2, 1)),
+                     mk([rng.randrange(groth16.R) for _ in range(3)]))]
+    else:
+        cc = compile_circuit(circuits.AddressCircuitCommit(), 16)
+        rng = random.Random(56)
+        distinct = []
+        for _ in range(4):
+            pub = pyref.secp256k1_mul(rng.randrange(1, pyref.SECP_N))
+            distinct.append(to_mont_array(cc.assignment_vector(
+                {"Address": pyref.eth_address(pub), "X": limbs_of(pub[0]), "Y": limbs_of(pub[1])})))
     inp = np.stack([distinct[i % len(distinct)] for i in range(ADDRESS_BATCH)])
     rs = np.stack([to_mont_array([rng.randrange(groth16.R), rng.randrange(groth16.R)])
                    for _ in range(ADDRESS_BATCH)])
@@ -69,7 +82,7 @@ def _setup_address(need_key):
 
 
 def _setup(need_key):
-    if WORKLOAD == "address-commit":
+    if WORKLOAD in COMMITTED:
         return _setup_address(need_key)
     import numpy as np
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
@@ -111,7 +124,7 @@ def step_solve_address():
     for which in ("r1cs", "program"):
         submit = prover.submit if which == "program" else prover.submit_r1cs
         if which == "r1cs":
-            info = ctx.r1cs_solver_info(prover.load_r1cs_solver(0, hints="std"))
+            info = ctx.r1cs_solver_info(prover.load_r1cs_solver(0, hints=COMMITTED[WORKLOAD]))
             out["instr"] = {k: info[k] for k in ("n_instr", "n_terms", "longest", "n_inversions")}
         ms = []
         for n in range(4):                      # one warm-up, then three
@@ -128,7 +141,7 @@ def step_solve_address():
 
 
 def step_solve():
-    if WORKLOAD == "address-commit":
+    if WORKLOAD in COMMITTED:
         return step_solve_address()
     import numpy as np
     ctx, cc, prover, inp_d, _ = _setup(False)
@@ -153,7 +166,7 @@ def step_pipe(which, steps):
     ctx, cc, prover, inp_d, rs_d = _setup(True)
     submit = prover.submit if which == "program" else prover.submit_r1cs
     if which == "r1cs":
-        prover.load_r1cs_solver(0, hints="std" if WORKLOAD == "address-commit" else "basic")
+        prover.load_r1cs_solver(0, hints=COMMITTED.get(WORKLOAD, "basic"))
     batch = inp_d.shape[0]
 
     def run(n):
@@ -176,7 +189,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--step", choices=tuple(STEP_LIMIT_S), help="run one step in this process")
     ap.add_argument("--steps", type=int, default=12, help="batches of a pipelined step (at least 10)")
-    ap.add_argument("--workload", choices=("arbo160", "address-commit"), default="arbo160")
+    ap.add_argument("--workload", choices=("arbo160", "address-commit", "emulated-poseidon"), default="arbo160")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     if args.steps < 10:
@@ -190,6 +203,8 @@ def main():
     result = {"circuit": f"smt_inclusion_circuit({LEVELS})", "batch": BATCH, "populated": POPULATED}
     if WORKLOAD == "address-commit":
         result = {"circuit": "AddressCircuitCommit", "batch": ADDRESS_BATCH}
+    if WORKLOAD == "emulated-poseidon":
+        result = {"circuit": "EmulatedPoseidonCircuit", "batch": ADDRESS_BATCH}
     rc = 0
     for step, limit in STEP_LIMIT_S.items():
         # a fresh child per step; killed at its limit; after a failure nothing more runs on the GPU
