@@ -15,13 +15,17 @@ using namespace zk;
 
 namespace zk {
 
+void sync_side_streams(zkmi_ctx* ctx) {
+  for (hipStream_t q : {ctx->stream2, ctx->stream3, ctx->stream4})
+    if (q) hipStreamSynchronize(q);
+}
+
 int ensure_scratch(zkmi_ctx* ctx, DevBuf& s, size_t bytes, void** out) {
   if (s.bytes < bytes) {
     if (s.p) {
       // nothing queued on any of the context's streams may still use the old buffer
       hipStreamSynchronize(ctx->stream);
-      if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
-      if (ctx->stream3) hipStreamSynchronize(ctx->stream3);
+      sync_side_streams(ctx);
       hipFree(s.p);
       s.p = nullptr;
       s.bytes = 0;
@@ -330,7 +334,7 @@ int prove_set_end(zkmi_ctx* ctx, hipStream_t main, int rc) {
   hipEventRecord(S.ev1, ctx->stream);
   ctx->stream = main;
   if (rc) {
-    hipStreamSynchronize(ctx->stream2);   // nothing of a failed submit stays queued on caller memory
+    sync_side_streams(ctx);   // nothing of a failed submit stays queued on caller memory
     return rc;
   }
   S.pending = true;
@@ -367,11 +371,19 @@ int zkmi_init(int device, zkmi_ctx** out) {
     delete ctx;
     return ZKMI_ERR_HIP;
   }
+  if (hipStreamCreateWithFlags(&ctx->stream4, hipStreamNonBlocking) != hipSuccess) {
+    hipStreamDestroy(ctx->stream3);
+    hipStreamDestroy(ctx->stream2);
+    hipStreamDestroy(ctx->stream);
+    delete ctx;
+    return ZKMI_ERR_HIP;
+  }
   for (auto& st : ctx->sets) {
     hipEventCreate(&st.ev0);
     hipEventCreate(&st.ev1);
     for (auto& e : st.evq) hipEventCreate(&e);
     for (auto& e : st.eva) hipEventCreate(&e);
+    hipEventCreateWithFlags(&st.tail_ev, hipEventDisableTiming);
     for (auto& p : st.msm_ev) {
       hipEventCreate(&p[0]);
       hipEventCreate(&p[1]);
@@ -380,6 +392,7 @@ int zkmi_init(int device, zkmi_ctx** out) {
   for (auto& e : ctx->ev) hipEventCreate(&e);
   for (auto& e : ctx->part_ev) hipEventCreateWithFlags(&e, hipEventDisableTiming);
   for (auto& e : ctx->acc_ev) hipEventCreateWithFlags(&e, hipEventDisableTiming);
+  for (auto& e : ctx->dig_ev) hipEventCreateWithFlags(&e, hipEventDisableTiming);
   ctx->plans.reserve(32);
   *out = ctx;
   return ZKMI_OK;
@@ -389,8 +402,7 @@ void zkmi_destroy(zkmi_ctx* ctx) {
   if (!ctx) return;
   hipSetDevice(ctx->device);
   hipStreamSynchronize(ctx->stream);
-  hipStreamSynchronize(ctx->stream2);
-  hipStreamSynchronize(ctx->stream3);
+  sync_side_streams(ctx);
   for (auto& st : ctx->sets) {
     if (st.ev0) hipEventDestroy(st.ev0);
     if (st.ev1) hipEventDestroy(st.ev1);
@@ -398,6 +410,7 @@ void zkmi_destroy(zkmi_ctx* ctx) {
       if (e) hipEventDestroy(e);
     for (auto& e : st.eva)
       if (e) hipEventDestroy(e);
+    if (st.tail_ev) hipEventDestroy(st.tail_ev);
     for (auto& p : st.msm_ev) {
       if (p[0]) hipEventDestroy(p[0]);
       if (p[1]) hipEventDestroy(p[1]);
@@ -405,6 +418,7 @@ void zkmi_destroy(zkmi_ctx* ctx) {
   }
   hipStreamDestroy(ctx->stream2);
   hipStreamDestroy(ctx->stream3);
+  hipStreamDestroy(ctx->stream4);
   for (auto& p : ctx->plans) free_plan(p);
   for (auto& st : ctx->sets)
     for (DevBuf* b : {&st.slots, &st.a, &st.b, &st.c, &st.misc, &st.sums, &st.commit})
@@ -418,6 +432,8 @@ void zkmi_destroy(zkmi_ctx* ctx) {
   for (auto& e : ctx->part_ev)
     if (e) hipEventDestroy(e);
   for (auto& e : ctx->acc_ev)
+    if (e) hipEventDestroy(e);
+  for (auto& e : ctx->dig_ev)
     if (e) hipEventDestroy(e);
   hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -622,7 +638,8 @@ static WinPlan plan_explicit(int wb) {
 }
 // HBM the prover needs beside the tables to prove batches of up to `max_batch` with a key of this
 // shape: two pipeline sets (value file, a, b, c, staged inputs, sums, commitment
-// buffers), the NTT scratch, the MSM integer scalars + digits + two partial-sum buffers, the
+// buffers), the NTT scratch, the MSM integer scalars + digits + two partial-sum buffers (with what
+// the MSM tails read beside the sums: lane-0 digits and the list of the uniform groups), the
 // table-build scratch that stays allocated, and a margin for the allocator.
 static double prove_working_set_bytes(uint32_t log_n, size_t n_slots, size_t n_in, size_t max_batch,
                                       size_t n_msm_max, size_t n_commitments) {
@@ -633,7 +650,9 @@ static double prove_working_set_bytes(uint32_t log_n, size_t n_slots, size_t n_i
                               commit_buffer_bytes(n_commitments, Bp));
   const double digits = 254.0 * (double)((n_msm_max + 15) / 16) * Bp * 4;   // comb, k >= 16
   const double sint = (double)n_msm_max * Bp * 32;
-  const double partials = 2 * 21.0 * 254 * Bp * 256;
+  // two partial-sum buffers (msm_part_layout.h): 21 blocks of [255][Bp] G2 accumulators, lane 0's
+  // digits of the uniform groups [255][G] and the list of those groups [G], as the digits at k >= 16
+  const double partials = 2 * (21.0 * 254 * Bp * 256 + 256.0 * (double)((n_msm_max + 15) / 16) * 4);
   // device half of the witness entry's staging ring (witness.hip): three chunks of ~64 MB, or of
   // one 64-proof column block of the wire matrix when that is larger (n_in = n_wires here)
   const double ring = 3.0 * std::max(68e6, (double)n_in * 32 * 64);
@@ -1320,8 +1339,9 @@ int zkmi_prove_submit(zkmi_ctx* ctx, const zkmi_pk* pk, const zkmi_cs* cs, const
 }
 
 // The ALU-heavy part of stage 2 (quotient, five MSMs, the one-base delta MSMs) of set `si`, on the
-// main stream.  Everything it touches besides the set's own buffers (NTT scratch, MSM partials) is
-// only used on the main stream, so consecutive batches simply queue up behind each other.
+// main stream.  Everything it touches besides the set's own buffers (NTT scratch, MSM digits) is
+// only used on the main stream, so consecutive batches simply queue up behind each other; the two
+// MSM partial-sum buffers are also read by the MSM tails on stream4, under part_ev (msm_impl.h).
 static int enqueue_heavy(zkmi_ctx* ctx, int si) {
   zkmi_ctx::ProveSet& S = ctx->sets[si];
   const zkmi_pk* pk = S.pk;
@@ -1350,7 +1370,10 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
   // shared-table plans: stop at the window sums, the Horner step runs with the assembly
   const bool d1 = pk->Z->plan.shared || pk->Z->plan.comb;
   const bool d2 = pk->B2->plan.shared || pk->B2->plan.comb;
-  hipStream_t q3 = ctx->stream3;
+  // The tails of the five MSMs (msm_run's finish stream) run on stream4, not on the assembly
+  // stream: there the tail of this batch's A would queue behind the previous batch's assembly
+  // (~26 ms), and K, which takes A's partial-sum buffer, would hold the main stream until it is read.
+  hipStream_t q3 = ctx->stream3, q4 = ctx->stream4;
   // comb plans: A, B1, K and B2 walk overlapping rows of the value file, so which wires vary over
   // the batch is found once for all four; the quotient's scalars are dense
   uint8_t* rv = nullptr;
@@ -1363,22 +1386,24 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
     }
     rv = (uint8_t*)p;
   }
-  if ((rc = msm_run(ctx, pk->A, slots, pk->a_wire, Bp, batch, v.sA, fd, d1 ? v.w1[0] : nullptr, q3,
+  if ((rc = msm_run(ctx, pk->A, slots, pk->a_wire, Bp, batch, v.sA, fd, d1 ? v.w1[0] : nullptr, q4,
                     rv)) ||
-      (rc = msm_run(ctx, pk->B1, slots, pk->b_wire, Bp, batch, v.sB1, fd, d1 ? v.w1[1] : nullptr, q3,
+      (rc = msm_run(ctx, pk->B1, slots, pk->b_wire, Bp, batch, v.sB1, fd, d1 ? v.w1[1] : nullptr, q4,
                     rv)) ||
-      (rc = msm_run(ctx, pk->K, slots, pk->k_wire, Bp, batch, v.sK, fd, d1 ? v.w1[2] : nullptr, q3,
+      (rc = msm_run(ctx, pk->K, slots, pk->k_wire, Bp, batch, v.sK, fd, d1 ? v.w1[2] : nullptr, q4,
                     rv)) ||
-      (rc = msm_run(ctx, pk->Z, h, nullptr, Bp, batch, v.sZ, false, d1 ? v.w1[3] : nullptr, q3,
+      (rc = msm_run(ctx, pk->Z, h, nullptr, Bp, batch, v.sZ, false, d1 ? v.w1[3] : nullptr, q4,
                     nullptr, true))) {
     ctx->msm_ev_set = -1;
     return rc;
   }
   hipEventRecord(S.evq[2], ctx->stream);
-  rc = msm_run(ctx, pk->B2, slots, pk->b_wire, Bp, batch, v.sB2, fd, d2 ? v.w2 : nullptr, q3, rv);
+  rc = msm_run(ctx, pk->B2, slots, pk->b_wire, Bp, batch, v.sB2, fd, d2 ? v.w2 : nullptr, q4, rv);
   ctx->msm_ev_set = -1;
   if (rc) return rc;
   hipEventRecord(S.evq[3], ctx->stream);
+  // stream4 is in order: behind B2's tail, the window sums of all five MSMs are complete
+  ZK_HIP(hipEventRecord(S.tail_ev, q4));
   // The multiples of delta (r, s, -rs times delta1; s times delta2) are four one-base MSMs of sixteen
   // wavefronts each: latency, not work.  They run on the assembly stream, which is where their
   // results are used, with their own partial-sum scratch (side = 2) -- on the main stream they were
@@ -1429,6 +1454,7 @@ int zkmi_prove_collect_ex(zkmi_ctx* ctx, void* proofs_out, int32_t* status_out,
   SumsView v(S.sums.p, Bp);
   hipStream_t q3 = ctx->stream3;
   ZK_HIP(hipStreamWaitEvent(q3, S.evq[4], 0));
+  ZK_HIP(hipStreamWaitEvent(q3, S.tail_ev, 0));   // the window sums the Horner steps read
   hipEventRecord(S.eva[0], q3);
   if (pk->Z->plan.shared || pk->Z->plan.comb) {
     void* ws[4] = {v.w1[0], v.w1[1], v.w1[2], v.w1[3]};
@@ -1476,8 +1502,8 @@ int zkmi_prove_collect_ex(zkmi_ctx* ctx, void* proofs_out, int32_t* status_out,
   // look ahead: queue the next batch's heavy kernels before blocking on this batch's assembly
   zkmi_ctx::ProveSet& N = ctx->sets[si ^ 1];
   if (N.pending && !N.heavy_enqueued && (rc = enqueue_heavy(ctx, si ^ 1))) return rc;
-  // wait for THIS batch's copies only: the look-ahead has queued the next batch's MSM tails behind
-  // them on the same stream
+  // wait for THIS batch's copies only: the look-ahead has queued the next batch's multiples of
+  // delta behind them on the same stream
   ZK_HIP(hipEventSynchronize(S.eva[1]));
   S.pending = false;
   S.heavy_enqueued = false;

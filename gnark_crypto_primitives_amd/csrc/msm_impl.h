@@ -7,6 +7,7 @@
 #include "zkmi_internal.h"
 #include "ec29.h"
 #include "comb_sign.h"
+#include "msm_part_layout.h"
 
 namespace zk {
 
@@ -1050,26 +1051,38 @@ static void reduce_partials(hipStream_t stream, const XYZZ<F>* partial, XYZZ<F>*
                      (const Part29<F>*)addend, counts, (uint32_t)cs.chunks, div);
 }
 
-// msm_part[pb] of the comb and shared-table routines: the chunk partials [W][chunks][Bp], the group
-// sums [W][ngroups][Bp], the window sums [W][Bp] (unused when the caller takes them), and for comb
-// tables the W common sums of the uniform groups and the two counts of comb_split_kernel.  Only
-// wsum holds XYZZ<F> values: the other sums are packed accumulators of the same size (Part29<F>,
-// ec29.h).  The counts are here and not beside the group lists because the reduction reads them,
-// possibly on the finish stream while the main stream already splits the next MSM's groups.
+// msm_part[pb] of the comb and shared-table routines (msm_part_layout.h has the regions and their
+// order): the chunk partials [W][chunks][Bp], the group sums [W][ngroups][Bp], the window sums
+// [W][Bp] (unused when the caller takes them), and for comb tables everything else the tail of the
+// MSM reads: the W common sums of the uniform groups, the two counts of comb_split_kernel, lane 0's
+// digits of the uniform groups d0 [W][G] and the list of those groups ulist [G].  Only wsum holds
+// XYZZ<F> values: the other sums are packed accumulators of the same size (Part29<F>, ec29.h).
+// The tail (comb_common_sums, msm_reduce) may run on the finish stream while the main stream
+// already splits the next MSM's groups and writes its digits, hence the invariant: nothing the
+// tail stream reads is written by the main stream between wait_partials_free(pb) and the next
+// part_ev[pb].  vlist, vpos and the per-lane digits are read on the main stream only and live in
+// msm_digits.
 template <class F>
 struct PartView {
   XYZZ<F> *partial, *mid, *wsum, *usum;
-  uint32_t* counts;
-  static size_t bytes(const ChunkSplit& cs, int W, size_t Bp, bool common_sums) {
-    return ((cs.chunks + cs.ngroups + 1) * W * Bp + (common_sums ? W : 0)) * sizeof(XYZZ<F>) +
-           (common_sums ? 2 * sizeof(uint32_t) : 0);
+  uint32_t *counts, *d0, *ulist;
+  static MsmPartLayout layout(const ChunkSplit& cs, int W, size_t Bp, size_t G, bool common_sums) {
+    return msm_part_layout(sizeof(XYZZ<F>), cs.chunks, cs.ngroups, (size_t)W, Bp, G, common_sums);
   }
-  PartView(void* base, const ChunkSplit& cs, int W, size_t Bp) {
-    partial = (XYZZ<F>*)base;
-    mid = partial + cs.chunks * W * Bp;
-    wsum = mid + (size_t)cs.ngroups * W * Bp;
-    usum = wsum + (size_t)W * Bp;
-    counts = (uint32_t*)(usum + W);
+  static size_t bytes(const ChunkSplit& cs, int W, size_t Bp, size_t G, bool common_sums) {
+    return layout(cs, W, Bp, G, common_sums).bytes();
+  }
+  PartView(void* base, const ChunkSplit& cs, int W, size_t Bp, size_t G, bool common_sums) {
+    static_assert(sizeof(XYZZ<F>) == sizeof(Part29<F>), "packed accumulators share the regions");
+    const MsmPartLayout l = layout(cs, W, Bp, G, common_sums);
+    char* m = (char*)base;
+    partial = (XYZZ<F>*)(m + l.off[MSM_PART_PARTIAL]);
+    mid = (XYZZ<F>*)(m + l.off[MSM_PART_MID]);
+    wsum = (XYZZ<F>*)(m + l.off[MSM_PART_WSUM]);
+    usum = (XYZZ<F>*)(m + l.off[MSM_PART_USUM]);
+    counts = (uint32_t*)(m + l.off[MSM_PART_COUNTS]);
+    d0 = (uint32_t*)(m + l.off[MSM_PART_D0]);
+    ulist = (uint32_t*)(m + l.off[MSM_PART_ULIST]);
   }
 };
 
@@ -1118,27 +1131,22 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
   // writes the other partial buffer
   const bool defer = wsum_out && finish_stream && finish_stream != ctx->stream;
   const int pb = defer ? (int)(ctx->part_next++ & 1u) : 0;
-  // (the common sums and the counts are read by the reduction, which may run on finish_stream:
-  // they are under part_ev as well)
-  int rc = ensure_scratch(ctx, ctx->msm_part[pb], PartView<F>::bytes(cs, W, Bp, true), &part);
+  // (everything the tail reads, possibly on finish_stream, is in this buffer, under part_ev)
+  int rc = ensure_scratch(ctx, ctx->msm_part[pb], PartView<F>::bytes(cs, W, Bp, G, true), &part);
   if (rc) return rc;
   if ((rc = wait_partials_free(ctx, pb))) return rc;
   // (Measured and dropped: the digit pass one MSM ahead on a fourth stream through two digit
   // buffers -- correct, no gain: the pass is ALU work like the accumulate kernel it would hide
   // under, which slowed down by exactly the pass's 7 ms.)
-  // digits [W][G][Bp] (the first |vlist| rows of every window are used), then lane 0's digits of
-  // the uniform groups [W][G], the split of the groups: vlist, ulist, vpos [G], and the flags of
-  // the bases [n] when the caller brings none
+  // digits [W][G][Bp] (the first |vlist| rows of every window are used), then what else only the
+  // main stream reads: vlist, vpos [G], and the flags of the bases [n] when the caller brings none
   if ((rc = ensure_scratch(ctx, ctx->msm_digits,
-                           ((size_t)W * G * Bp + (size_t)(W + 3) * G) * sizeof(uint32_t) + n,
-                           &digits)))
+                           ((size_t)W * G * Bp + (size_t)2 * G) * sizeof(uint32_t) + n, &digits)))
     return rc;
-  uint32_t* d0 = (uint32_t*)digits + (size_t)W * G * Bp;
-  uint32_t* vlist = d0 + (size_t)W * G;
-  uint32_t* ulist = vlist + G;
-  uint32_t* vpos = ulist + G;
-  const PartView<F> pv(part, cs, W, Bp);
-  uint32_t* counts = pv.counts;
+  uint32_t* vlist = (uint32_t*)digits + (size_t)W * G * Bp;
+  uint32_t* vpos = vlist + G;
+  const PartView<F> pv(part, cs, W, Bp, G, true);
+  uint32_t *counts = pv.counts, *d0 = pv.d0, *ulist = pv.ulist;
   XYZZ<F>* wsum = wsum_out ? wsum_out : pv.wsum;
   const unsigned bx = (Bp % 256 == 0) ? 256 : 64;
   const dim3 dgrid((unsigned)(Bp / bx), (unsigned)(G < 8192 ? G : 8192));
@@ -1174,8 +1182,6 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
   hipLaunchKernelGGL((sg ? comb_digits_kernel<21, true> : comb_digits_kernel<20, false>), dgrid,
                      dim3(bx), 0, ctx->stream, dsrc, didx, Bp, (uint32_t)n, k, (uint32_t)G,
                      (const uint32_t*)vpos, (uint32_t*)digits, d0);
-  // timed: the common sums and the accumulate launch, every mixed addition
-  const hipEvent_t timed = acc_timer_begin(ctx, bases);
   const dim3 grid((unsigned)(Bp / bx), (unsigned)W, (unsigned)cs.chunks);
   const uint32_t per_group = 1u << (sg ? k - 1 : k);
   const bool ci = bases->entries_may_be_inf != 0;
@@ -1184,21 +1190,33 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
   const auto accumulate =
       ci ? (sg ? msm_accumulate_comb<F, true, true> : msm_accumulate_comb<F, true, false>)
          : (sg ? msm_accumulate_comb<F, false, true> : msm_accumulate_comb<F, false, false>);
-  hipLaunchKernelGGL(sums, dim3((unsigned)W), dim3(256), 0, ctx->stream,
-                     (const Affine<F>*)bases->table, (const uint32_t*)d0, (uint32_t)G,
-                     (const uint32_t*)ulist, (const uint32_t*)counts, per_group,
-                     (Part29<F>*)pv.usum);
+  // The tail: the common sums of the uniform groups, then the sums over the chunk partials.  Only
+  // the last reduction pass reads the common sums, so with a deferred tail they run on the finish
+  // stream beside the accumulate launch (255 workgroups: one wave per SIMD on a quarter of the
+  // chip), ordered after the split and the digit pass by dig_ev.  A dense MSM has no uniform group:
+  // no launch, no addend.
+  hipStream_t rq = defer ? finish_stream : ctx->stream;
+  const XYZZ<F>* addend = nullptr;
+  if (!dense) {
+    if (defer) {
+      ZK_HIP(hipEventRecord(ctx->dig_ev[pb], ctx->stream));
+      ZK_HIP(hipStreamWaitEvent(rq, ctx->dig_ev[pb], 0));
+    }
+    hipLaunchKernelGGL(sums, dim3((unsigned)W), dim3(256), 0, rq, (const Affine<F>*)bases->table,
+                       (const uint32_t*)d0, (uint32_t)G, (const uint32_t*)ulist,
+                       (const uint32_t*)counts, per_group, (Part29<F>*)pv.usum);
+    addend = pv.usum;
+  }
+  const hipEvent_t timed = acc_timer_begin(ctx, bases);   // the accumulate launch alone
   hipLaunchKernelGGL(accumulate, grid, dim3(bx), 0, ctx->stream, (const Affine<F>*)bases->table,
                      (const uint32_t*)digits, Bp, (uint32_t)G, (const uint32_t*)vlist,
                      (const uint32_t*)counts, per_group, (Part29<F>*)pv.partial);
   acc_timer_end(ctx, timed);
-  hipStream_t rq = ctx->stream;
   if (defer) {
     ZK_HIP(hipEventRecord(ctx->acc_ev[pb], ctx->stream));
-    ZK_HIP(hipStreamWaitEvent(finish_stream, ctx->acc_ev[pb], 0));
-    rq = finish_stream;
+    ZK_HIP(hipStreamWaitEvent(rq, ctx->acc_ev[pb], 0));
   }
-  reduce_partials<F>(rq, pv.partial, pv.mid, wsum, Bp, cs, W, pv.usum, counts);
+  reduce_partials<F>(rq, pv.partial, pv.mid, wsum, Bp, cs, W, addend, counts);
   if (defer) {
     ZK_HIP(hipEventRecord(ctx->part_ev[pb], finish_stream));
     ctx->part_ev_valid[pb] = true;
@@ -1234,12 +1252,12 @@ int run_shared(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars,
   const size_t shared_factor = bases->chunk_factor ? bases->chunk_factor : 8;
   const ChunkSplit cs = split_chunks(n, shared_factor * 262144 / Bp / (size_t)W);
   void *part, *digits;
-  int rc = ensure_scratch(ctx, ctx->msm_part[0], PartView<F>::bytes(cs, W, Bp, false), &part);
+  int rc = ensure_scratch(ctx, ctx->msm_part[0], PartView<F>::bytes(cs, W, Bp, 0, false), &part);
   if (rc) return rc;
   if ((rc = wait_partials_free(ctx, 0))) return rc;
   if ((rc = ensure_scratch(ctx, ctx->msm_digits, (size_t)W * n * Bp * sizeof(int16_t), &digits)))
     return rc;
-  const PartView<F> pv(part, cs, W, Bp);
+  const PartView<F> pv(part, cs, W, Bp, 0, false);
   // window sums: into the caller's buffer when the Horner step is deferred (msm_horner_run)
   XYZZ<F>* wsum = wsum_out ? wsum_out : pv.wsum;
   const unsigned bx = (Bp % 256 == 0) ? 256 : 64;

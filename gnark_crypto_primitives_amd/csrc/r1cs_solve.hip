@@ -450,7 +450,7 @@ void zkmi_r1cs_solver_free(zkmi_ctx* ctx, zkmi_r1cs_solver* s) {
   if (ctx) {
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
+    sync_side_streams(ctx);
   }
   if (s->records) hipFree(s->records);
   if (s->terms) hipFree(s->terms);

@@ -261,7 +261,7 @@ void zkmi_r1cs_free(zkmi_ctx* ctx, zkmi_r1cs* m) {
   if (ctx) {
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    if (ctx->stream2) hipStreamSynchronize(ctx->stream2);
+    sync_side_streams(ctx);
   }
   for (int s = 0; s < 3; s++) {
     if (m->ptr[s]) hipFree(m->ptr[s]);

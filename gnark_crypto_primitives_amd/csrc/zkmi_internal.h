@@ -65,7 +65,9 @@ struct zkmi_ctx {
   zk::DevBuf build_tmp;              // table-build inversion scratch; proof-of-knowledge temporary
   zk::DevBuf msm_digits, msm_sint;   // MSM digits, converted scalars (comb_scalars_kernel)
   zk::DevBuf msm_rowvar;             // which value-file rows vary over the batch (enqueue_heavy)
-  zk::DevBuf msm_part[2];            // MSM chunk partials; [1] only for deferred tails (part_ev)
+  // MSM chunk partials and what else an MSM's tail reads (msm_part_layout.h); [1] only for
+  // deferred tails (part_ev)
+  zk::DevBuf msm_part[2];
   // Side bases (zkmi_msm_bases::side) run while the main stream may be running an MSM on
   // msm_part[0], so each side stream has its own partials:
   zk::DevBuf side_part2;             // stream2: commitment MSMs of a submit
@@ -73,7 +75,11 @@ struct zkmi_ctx {
   // software pipeline over batches: the latency-bound witness solve of batch k+1 runs on
   // `stream2` (16 wavefronts at batch 1024) underneath the NTT/MSM kernels of batch k.
   // `stream3` runs the 16-wavefront assembly of batch k underneath the quotient kernels of batch k+1.
-  hipStream_t stream2 = nullptr, stream3 = nullptr;
+  // `stream4` runs the tail of every proving-key MSM (common sums, sums over the chunk partials)
+  // beside the next MSM's kernels.  It is a stream of its own because the tail of batch k+1's
+  // first MSMs must not queue behind batch k's assembly on stream3: the main stream waits for it
+  // (part_ev) before it reuses a partial-sum buffer.
+  hipStream_t stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;
   struct ProveSet {
     bool pending = false;
     bool heavy_enqueued = false;   // quotient + MSMs of this batch are already on the main stream
@@ -84,6 +90,7 @@ struct zkmi_ctx {
     zk::DevBuf slots, a, b, c, misc, sums, commit;
     hipEvent_t evq[5] = {};        // main stream: start, after NTTs, after G1 MSMs, after G2, done
     hipEvent_t eva[2] = {};        // stream3: assembly start / end
+    hipEvent_t tail_ev = nullptr;  // stream4: the window sums of all five MSMs are complete
     hipEvent_t msm_ev[8][2] = {};  // around every proving-key msm_accumulate launch
     int msm_ev_group[8] = {};
     int msm_ev_used = 0;
@@ -106,8 +113,9 @@ struct zkmi_ctx {
   int msm_ev_set = -1;
   // deferred MSM tails (msm_run with a finish stream): the chunk partials of consecutive MSMs
   // alternate between two buffers; part_ev[k] = last reduction that read buffer k has finished
-  // (recorded on the finish stream), acc_ev[k] = last accumulate that wrote it (main stream)
-  hipEvent_t part_ev[2] = {}, acc_ev[2] = {};
+  // (recorded on the finish stream), acc_ev[k] = last accumulate that wrote it (main stream),
+  // dig_ev[k] = the split and digit kernels that wrote its lists and lane-0 digits (main stream)
+  hipEvent_t part_ev[2] = {}, acc_ev[2] = {}, dig_ev[2] = {};
   bool part_ev_valid[2] = {false, false};
   unsigned part_next = 0;
   // witness entry (witness.hip): ring of three pinned host chunks + three device chunks through
@@ -255,6 +263,8 @@ __device__ __forceinline__ void bi_st_nt(Fr* base, size_t row, size_t b, size_t 
 
 static inline size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
+// waits for everything queued on the context's side streams (stream2, stream3, stream4)
+void sync_side_streams(zkmi_ctx* ctx);
 // grows `buf` to at least `bytes` (synchronising the context's streams first if it held memory)
 int ensure_scratch(zkmi_ctx* ctx, DevBuf& buf, size_t bytes, void** out = nullptr);
 // ZKMI_OK when no Groth16 batch is in flight, else ZKMI_ERR_ARG with ctx->err set
@@ -395,9 +405,11 @@ int msm_bases_build(zkmi_ctx* ctx, int group, const void* bases_dev, size_t n, c
 // With wsum_out (shared-table and comb plans only) msm_run stops at the W window sums ([W][Bp] XYZZ)
 // and the caller finishes with msm_horner_run -- 255 dependent doublings per proof, latency-bound,
 // which the prover runs on its assembly stream under the next batch's kernels.  With finish_stream
-// (comb plans) the sums over the chunk partials run there too (ordered after the accumulate launch
-// by an event; the partials of consecutive MSMs alternate between two buffers), so the main stream
-// holds nothing but the digit pass and the accumulate kernel.
+// (comb plans; the prover passes stream4) the tail of the MSM runs there: the common sums of the
+// uniform groups (ordered after the digit pass by an event) and the sums over the chunk partials
+// (ordered after the accumulate launch by another; the partials of consecutive MSMs alternate
+// between two buffers), so the main stream holds nothing but the split, the digit pass and the
+// accumulate kernel.
 // Comb plans, which groups are uniform: row_varies (device, may be null) = msm_rows_vary's flags
 // of the rows of `scalars`, shared by every MSM that reads the same rows; dense = do not look,
 // every group varies (scalars with no structure, such as the quotient's).  With neither, msm_run

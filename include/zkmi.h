@@ -544,8 +544,9 @@ int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const 
  * pointwise; with a folded key the transforms of a and b alone), [2] G1 MSMs, [3] G2 MSM, [4] assembly (third stream; overlaps the next batch's
  * quotient when one is submitted), [5] main-stream span = [1] + [2] + [3] + delta multiples,
  * [6] sum over the four G1 msm_accumulate launches alone (one event pair around each launch),
- * [7] the G2 msm_accumulate launch alone.  With comb tables a pair also brackets the launch that
- * sums the groups whose scalars the whole batch shares, so it covers every mixed addition. */
+ * [7] the G2 msm_accumulate launch alone.  With comb tables the launch that sums the groups whose
+ * scalars the whole batch shares is outside the pair: it runs beside the accumulate launch, on the
+ * stream of the MSM tails. */
 int zkmi_last_timings(zkmi_ctx* ctx, double* ms_out /* 8 doubles */);
 
 #ifdef __cplusplus
