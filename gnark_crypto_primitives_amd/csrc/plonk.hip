@@ -16,7 +16,9 @@
 #include <algorithm>
 
 #include "zkmi_internal.h"
+#include "scs_check.h"
 #include "sha256.h"
+#include <atomic>
 #include <cstring>
 #include "ff29.h"
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -33,6 +35,10 @@ struct zkmi_plonk_pk {
   zkmi_msm_bases* lag[3] = {nullptr, nullptr, nullptr};   // Lagrange points of a, b, c (optional)
   uint32_t* lag_rows[3] = {nullptr, nullptr, nullptr};    // their scalar rows (device)
   uint32_t* chunk_idx = nullptr;   // 3 x (n + 6): scalar rows of t_lo / t_mid / t_hi in the 4n buffer
+  // a key loaded from its trace form keeps its permutation (3n positions, host) for the wiring check
+  // of the witness entry; `serial` names the key in the systems already checked against it
+  std::vector<uint32_t> perm;
+  uint64_t serial = 0;
   // state of the batch in flight
   size_t batch = 0, Bp = 0;
   int round = 0;
@@ -326,6 +332,85 @@ __global__ __launch_bounds__(64) void plonk_div_local(const Fr* N, const Fr* NZ,
   }
 }
 
+// ---- key from the trace form (zkmi_plonk_pk_load_trace): what the transforms do not compute -------
+// out[i] = first base^i, square and multiply over the bits of i: w^i, and 5 w_4n^j
+__global__ void plonk_powers_kernel(Fr* out, size_t count, Fr base, Fr first) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  Fr acc = first, b = base;
+  for (size_t e = i; e; e >>= 1) {
+    if (e & 1) acc = mul(acc, b);
+    b = sqr(b);
+  }
+  out[i] = acc;
+}
+// sigma[p] = k_c' w^r' for perm[p] = c' n + r', k = 1, 5, 25; the loader has checked perm[p] < 3n
+__global__ void plonk_sigma_kernel(const uint32_t* perm, const Fr* omega, Fr* sigma, uint32_t log_n,
+                                   Fr k1, Fr k2) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= ((size_t)3 << log_n)) return;
+  const uint32_t q = perm[p], c = q >> log_n;
+  const Fr v = omega[q & (((uint32_t)1 << log_n) - 1)];
+  sigma[p] = c == 0 ? v : mul(v, c == 1 ? k1 : k2);
+}
+// L_1(x) = (x^n - 1) / (n (x - 1)) at the coset points: x^n - 1 has period 4 there, zh_n[k] is its
+// value over n; one inversion per point (ff.h's inverse: the divsteps of modinv30.h)
+struct Fr4 {
+  Fr v[4];
+};
+__global__ __launch_bounds__(256) void plonk_l1_kernel(const Fr* xs, Fr* l1, size_t m, Fr4 zh_n) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  l1[j] = mul(zh_n.v[j & 3], inverse(sub(xs[j], Fr::one())));
+}
+
+// ---- round 1 from solved wires (zkmi_plonk_round1_witness) ------------------------------------------
+// One gate row per wavefront, 64 proofs per wavefront: the three wire indices, the marks and the
+// selectors of the row are wave-uniform (scalar loads), the wires three coalesced row reads of the
+// transposed wire matrix, the columns three row writes.  Gate value
+//     qL a + qR b + qO c + qM a b + qC + PI_g,   PI_g = -a_g for g < n_public
+// in gnark's image: qL qR qO qM are 2^261 images (fmulp: 256 + 261 - 261), a b = fmulp(a, 2^5 b)
+// likewise; a selector marked 0 / +1 / -1 (scs_check.h) takes no product.  Rows below n_public also
+// leave their a in `pub`, the public inputs round 3 and the transcript read.
+struct ScsDev {
+  const uint32_t* x[3];
+  const uint32_t* marks;
+  const Fr* sel;
+  uint32_t n_gates, n_public;
+};
+__device__ __forceinline__ Fr scs_term(uint32_t mark, const Fr& x, const Fr* q) {
+  if (mark == SCS_MARK_ZERO) return Fr::zero();
+  if (mark == SCS_MARK_ONE) return x;
+  if (mark == SCS_MARK_MINUS_ONE) return neg(x);
+  return fmulp(x, *q);
+}
+__global__ __launch_bounds__(256) void scs_gate_kernel(ScsDev s, const Fr* __restrict__ w,
+                                                       Fr* __restrict__ a, Fr* __restrict__ b,
+                                                       Fr* __restrict__ c, Fr* __restrict__ pub,
+                                                       int32_t* __restrict__ st, size_t Bp) {
+  const size_t p = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const size_t ng = s.n_gates;
+  for (uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6)); g < s.n_gates;
+       g += gridDim.y * 4) {
+    const uint32_t mk = s.marks[g];
+    const Fr va = bi_ld(w, s.x[0][g], p, Bp), vb = bi_ld(w, s.x[1][g], p, Bp),
+             vc = bi_ld(w, s.x[2][g], p, Bp);
+    bi_st(a, g, p, Bp, va);
+    bi_st(b, g, p, Bp, vb);
+    bi_st(c, g, p, Bp, vc);
+    Fr sum = add(add(scs_term(mk & 3, va, s.sel + g), scs_term((mk >> 2) & 3, vb, s.sel + ng + g)),
+                 scs_term((mk >> 4) & 3, vc, s.sel + 2 * ng + g));
+    const uint32_t mm = (mk >> 6) & 3;
+    if (mm != SCS_MARK_ZERO) sum = add(sum, scs_term(mm, fmulp(va, lift(vb, 5)), s.sel + 3 * ng + g));
+    if (((mk >> 8) & 3) != SCS_MARK_ZERO) sum = add(sum, s.sel[4 * ng + g]);
+    if (g < s.n_public) {
+      sum = sub(sum, va);
+      bi_st(pub, g, p, Bp, va);
+    }
+    if (!sum.is_zero()) st[p] = ZKMI_ERR_UNSATISFIED;
+  }
+}
+
 static int buf(zkmi_ctx* ctx, DevBuf& b, size_t bytes) {
   if (b.bytes >= bytes) return ZKMI_OK;
   if (b.p) {
@@ -396,34 +481,37 @@ void zkmi_plonk_pk_free(zkmi_ctx* ctx, zkmi_plonk_pk* pk) {
   delete pk;
 }
 
-int zkmi_plonk_pk_load(zkmi_ctx* ctx, const zkmi_plonk_pk_desc* d, zkmi_plonk_pk** out) {
-  ZK_HIP(hipSetDevice(ctx->device));
-  if (!d || !out) return ZKMI_ERR_ARG;
-  if (d->log_n < 4 || d->log_n > 24) {
+// What both loaders share.  pk_new: the checks on the domain and the empty key; pk_finish, once the
+// seven arrays of the key are on the device in gnark's image: the exponents the kernels expect, the
+// rows of the quotient chunks, the SRS tables, the Lagrange tables.  On failure the caller frees pk.
+struct PkCommon {
+  const void* srs_g1;
+  uint32_t window_bits;
+  const void* const* lag_g1;
+  const uint32_t* const* lag_rows;
+  uint32_t lag_k;
+};
+static int pk_new(zkmi_ctx* ctx, uint32_t log_n, uint32_t n_public, uint32_t max_batch,
+                  zkmi_plonk_pk** out) {
+  if (log_n < 4 || log_n > 24) {
     ctx->err = "plonk pk: log_n out of range [4,24]";
     return ZKMI_ERR_ARG;
   }
-  const size_t n = (size_t)1 << d->log_n, m = 4 * n;
-  if (d->n_public >= n) {
+  if (n_public >= (size_t)1 << log_n) {
     ctx->err = "plonk pk: more public inputs than gates";
     return ZKMI_ERR_ARG;
   }
+  static std::atomic<uint64_t> serial{0};
   auto* pk = new zkmi_plonk_pk();
-  pk->log_n = d->log_n;
-  pk->n_public = d->n_public;
-  pk->max_batch = d->max_batch ? d->max_batch : 64;
-  struct { Fr** dst; const void* src; size_t count; } up[7] = {
-      {&pk->coef, d->coef, 8 * n},   {&pk->coset, d->coset, 8 * m},   {&pk->sigma, d->sigma, 3 * n},
-      {&pk->omega, d->omega, n},     {&pk->coset_x, d->coset_x, m},   {&pk->l1, d->l1_coset, m},
-      {&pk->zh_inv, d->zh_inv, 4}};
-  for (auto& u : up) {
-    if (!u.src || hipMalloc((void**)u.dst, u.count * 32) != hipSuccess ||
-        hipMemcpy(*u.dst, u.src, u.count * 32, hipMemcpyDefault) != hipSuccess) {
-      ctx->err = "plonk pk: upload failed";
-      zkmi_plonk_pk_free(ctx, pk);
-      return ZKMI_ERR_HIP;
-    }
-  }
+  pk->log_n = log_n;
+  pk->n_public = n_public;
+  pk->max_batch = max_batch ? max_batch : 64;
+  pk->serial = ++serial;
+  *out = pk;
+  return ZKMI_OK;
+}
+static int pk_finish(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const PkCommon& k) {
+  const size_t n = (size_t)1 << pk->log_n, m = 4 * n;
   // exponents the quotient kernel expects (plonk_quotient): 2^261 images of qL qR qO S1 S2 S3 on the
   // coset, of the coset points, L_1 and 1 / Z_H; 2^266 of qM; qC as uploaded
   {
@@ -437,7 +525,6 @@ int zkmi_plonk_pk_load(zkmi_ctx* ctx, const zkmi_plonk_pk_desc* d, zkmi_plonk_pk
                            ctx->stream, l.p, l.count, l.k);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
       ctx->err = "plonk pk: key scaling failed";
-      zkmi_plonk_pk_free(ctx, pk);
       return ZKMI_ERR_HIP;
     }
   }
@@ -449,50 +536,62 @@ int zkmi_plonk_pk_load(zkmi_ctx* ctx, const zkmi_plonk_pk_desc* d, zkmi_plonk_pk
       for (size_t i = 0; i < n + 6; i++)
         idx[c * (n + 6) + i] = (uint32_t)(i < n + 2 ? c * (n + 2) + i : m - 1);
     if (hipMalloc((void**)&pk->chunk_idx, idx.size() * 4) != hipSuccess ||
-        hipMemcpy(pk->chunk_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(pk->chunk_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+      return ZKMI_ERR_HIP;
+  }
+  int rc = zkmi_msm_bases_load(ctx, 1, k.srs_g1, n + 6, (int)k.window_bits, &pk->srs);
+  if (rc) return rc;
+  if (k.lag_k) {   // after the SRS tables: these are small (2^k / k entries per point)
+    if (k.lag_k < 4 || k.lag_k > 16) {
+      ctx->err = "plonk pk: lag_k must be 0 or in [4,16]";
+      return ZKMI_ERR_ARG;
+    }
+    for (int c = 0; c < 3; c++) {
+      if (!k.lag_g1[c] || !k.lag_rows[c]) {
+        ctx->err = "plonk pk: lag_k set without lag_g1 / lag_rows";
+        return ZKMI_ERR_ARG;
+      }
+      std::vector<uint32_t> rows(n + 2);
+      if (hipMemcpy(rows.data(), k.lag_rows[c], (n + 2) * 4, hipMemcpyDefault) != hipSuccess)
+        return ZKMI_ERR_HIP;
+      for (uint32_t r : rows)
+        if (r >= n + 2) {
+          ctx->err = "plonk pk: lag_rows entry out of range";
+          return ZKMI_ERR_ARG;
+        }
+      if (hipMalloc((void**)&pk->lag_rows[c], (n + 2) * 4) != hipSuccess ||
+          hipMemcpy(pk->lag_rows[c], rows.data(), (n + 2) * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return ZKMI_ERR_HIP;
+      // 200 + k: subset-sum comb tables over groups of k points (zero digits are skipped)
+      if ((rc = zkmi_msm_bases_load(ctx, 1, k.lag_g1[c], n + 2, 200 + (int)k.lag_k, &pk->lag[c])))
+        return rc;
+    }
+  }
+  return ZKMI_OK;
+}
+
+int zkmi_plonk_pk_load(zkmi_ctx* ctx, const zkmi_plonk_pk_desc* d, zkmi_plonk_pk** out) {
+  ZK_HIP(hipSetDevice(ctx->device));
+  if (!d || !out) return ZKMI_ERR_ARG;
+  zkmi_plonk_pk* pk;
+  int rc = pk_new(ctx, d->log_n, d->n_public, d->max_batch, &pk);
+  if (rc) return rc;
+  const size_t n = (size_t)1 << d->log_n, m = 4 * n;
+  struct { Fr** dst; const void* src; size_t count; } up[7] = {
+      {&pk->coef, d->coef, 8 * n},   {&pk->coset, d->coset, 8 * m},   {&pk->sigma, d->sigma, 3 * n},
+      {&pk->omega, d->omega, n},     {&pk->coset_x, d->coset_x, m},   {&pk->l1, d->l1_coset, m},
+      {&pk->zh_inv, d->zh_inv, 4}};
+  for (auto& u : up) {
+    if (!u.src || hipMalloc((void**)u.dst, u.count * 32) != hipSuccess ||
+        hipMemcpy(*u.dst, u.src, u.count * 32, hipMemcpyDefault) != hipSuccess) {
+      ctx->err = "plonk pk: upload failed";
       zkmi_plonk_pk_free(ctx, pk);
       return ZKMI_ERR_HIP;
     }
   }
-  int rc = zkmi_msm_bases_load(ctx, 1, d->srs_g1, n + 6, (int)d->window_bits, &pk->srs);
-  if (rc) {
+  if ((rc = pk_finish(ctx, pk, PkCommon{d->srs_g1, d->window_bits, d->lag_g1, d->lag_rows, d->lag_k}))) {
     zkmi_plonk_pk_free(ctx, pk);
     return rc;
-  }
-  if (d->lag_k) {   // after the SRS tables: these are small (2^k / k entries per point)
-    if (d->lag_k < 4 || d->lag_k > 16) {
-      ctx->err = "plonk pk: lag_k must be 0 or in [4,16]";
-      zkmi_plonk_pk_free(ctx, pk);
-      return ZKMI_ERR_ARG;
-    }
-    for (int c = 0; c < 3; c++) {
-      if (!d->lag_g1[c] || !d->lag_rows[c]) {
-        ctx->err = "plonk pk: lag_k set without lag_g1 / lag_rows";
-        zkmi_plonk_pk_free(ctx, pk);
-        return ZKMI_ERR_ARG;
-      }
-      std::vector<uint32_t> rows(n + 2);
-      if (hipMemcpy(rows.data(), d->lag_rows[c], (n + 2) * 4, hipMemcpyDefault) != hipSuccess) {
-        zkmi_plonk_pk_free(ctx, pk);
-        return ZKMI_ERR_HIP;
-      }
-      for (uint32_t r : rows)
-        if (r >= n + 2) {
-          ctx->err = "plonk pk: lag_rows entry out of range";
-          zkmi_plonk_pk_free(ctx, pk);
-          return ZKMI_ERR_ARG;
-        }
-      if (hipMalloc((void**)&pk->lag_rows[c], (n + 2) * 4) != hipSuccess ||
-          hipMemcpy(pk->lag_rows[c], rows.data(), (n + 2) * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        zkmi_plonk_pk_free(ctx, pk);
-        return ZKMI_ERR_HIP;
-      }
-      // 200 + k: subset-sum comb tables over groups of k points (zero digits are skipped)
-      if ((rc = zkmi_msm_bases_load(ctx, 1, d->lag_g1[c], n + 2, 200 + (int)d->lag_k, &pk->lag[c]))) {
-        zkmi_plonk_pk_free(ctx, pk);
-        return rc;
-      }
-    }
   }
   *out = pk;
   return ZKMI_OK;
@@ -520,22 +619,13 @@ struct RoundTmp {
   }
 };
 
-// Round 1: witness solve (the constraint system's rows are the gate columns a, b, c), blinding,
-// commitments [a], [b], [c].
-int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
-                      size_t batch, const void* blind, void* commits_out, int32_t* status_out) {
-  ZK_HIP(hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = require_idle(ctx))) return rc;
-  if (batch == 0 || batch > pk->max_batch) {
-    ctx->err = "plonk: batch must be in [1, max_batch]";
-    return ZKMI_ERR_ARG;
-  }
+// Round 1 is shared by its two entries (zkmi_plonk_round1: the solver; zkmi_plonk_round1_witness:
+// solved wires) apart from how the columns come to be.  round1_begin: the batch's buffers;
+// round1_tail, with the Lagrange values of a, b, c in rows [0, nc) of big[1..3]: inverse transforms,
+// blinding (rows of small[0]), commitments in coefficient form or in the Lagrange basis.
+static int round1_begin(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch) {
   const size_t n = (size_t)1 << pk->log_n, m = 4 * n, Bp = round_up(batch, 64);
-  if (cs->n_constraints > n || cs->n_public - 1 != pk->n_public) {
-    ctx->err = "plonk: constraint system does not match the key";
-    return ZKMI_ERR_ARG;
-  }
+  int rc;
   pk->batch = batch;
   pk->Bp = Bp;
   pk->round = 0;
@@ -545,45 +635,22 @@ int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const
     if ((rc = buf(ctx, b, m * Bp * 32))) return rc;
   if ((rc = buf(ctx, pk->small[0], 16 * Bp * 32)) || (rc = buf(ctx, pk->small[1], 16 * Bp * 32)))
     return rc;
-  const size_t n_in = cs->n_public - 1 + cs->n_secret, nc = cs->n_constraints;
-  // stage inputs + blinding scalars (host or device, proof-major)
-  // value file and gate columns: big[0] = slots (reused later), big[1..3] = a, b, c; every size is
-  // checked before anything is staged
-  if ((size_t)cs->n_slots > m || n_in > m) {
-    ctx->err = "plonk: value file or input vector larger than the 4n work buffer";
-    return ZKMI_ERR_ARG;
-  }
-  RoundTmp tin(ctx), tbl(ctx);
-  if ((rc = tin.alloc(batch * n_in * 32)) || (rc = tbl.alloc(batch * 9 * 32))) return rc;
-  void *in_dev = tin.p, *bl_dev = tbl.p;
-  ZK_HIP(hipMemcpyAsync(in_dev, inputs, batch * n_in * 32, hipMemcpyDefault, ctx->stream));
-  ZK_HIP(hipMemcpyAsync(bl_dev, blind, batch * 9 * 32, hipMemcpyDefault, ctx->stream));
-  Fr* slots = (Fr*)pk->big[0].p;
+  return ZKMI_OK;
+}
+static int round1_tail(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t nc, void* commits_out) {
+  const size_t n = (size_t)1 << pk->log_n, Bp = pk->Bp, batch = pk->batch;
   Fr *A = (Fr*)pk->big[1].p, *B = (Fr*)pk->big[2].p, *C = (Fr*)pk->big[3].p;
-  void* st;
-  if ((rc = ensure_scratch(ctx, ctx->sets[0].misc, Bp * 4, &st))) return rc;
-  rc = transpose_in(ctx, in_dev, slots + Bp, n_in, batch, Bp, 32);
-  // the inputs in gnark's image, for PI(X) in round 3: big[5] rows 0 .. n_pub - 1 are the public ones
-  if (!rc) rc = transpose_in(ctx, in_dev, pk->big[5].p, n_in, batch, Bp, 32);
-  if (!rc) rc = rows_to_f_domain(ctx, slots + Bp, n_in, Bp);
-  if (!rc) rc = transpose_in(ctx, bl_dev, pk->small[0].p, 9, batch, Bp, 32);
-  if (!rc) rc = solve_bi(ctx, cs, slots, A, B, C, (int32_t*)st, Bp);
-  if (!rc) rc = rows_to_std_domain(ctx, A, nc, Bp);
-  if (!rc) rc = rows_to_std_domain(ctx, B, nc, Bp);
-  if (!rc) rc = rows_to_std_domain(ctx, C, nc, Bp);
-  // rows the solver does not write (padding gates) must read as zero in round 2
-  if (!rc && nc < n)
-    for (Fr* col : {A, B, C})
+  int rc;
+  Fr* cols[3] = {A, B, C};
+  // rows no gate writes (padding gates) must read as zero in round 2
+  if (nc < n)
+    for (Fr* col : cols)
       hipLaunchKernelGGL(plonk_zero_rows, dim3((unsigned)(Bp / 64), 64), dim3(64), 0, ctx->stream,
                          col, nc, n, Bp);
-  hipStreamSynchronize(ctx->stream);
-  if (rc) return rc;
-  ZK_HIP(hipMemcpy(status_out, st, batch * 4, hipMemcpyDefault));
   NttPlan* plan;
   if ((rc = get_plan(ctx, (int)pk->log_n, &plan))) return rc;
   const dim3 gl((unsigned)(Bp / 64));
   // columns (rows >= nc read as zero) -> coefficients -> blinded
-  Fr* cols[3] = {A, B, C};
   for (int k = 0; k < 3; k++) {
     Fr* cf = (Fr*)pk->cf[k].p;
     if ((rc = ntt_bi(ctx, plan, cols[k], cf, Bp, true, false, nc))) return rc;
@@ -613,6 +680,55 @@ int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const
   }
   pk->round = 1;
   return ZKMI_OK;
+}
+
+// Round 1: witness solve (the constraint system's rows are the gate columns a, b, c), blinding,
+// commitments [a], [b], [c].
+int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
+                      size_t batch, const void* blind, void* commits_out, int32_t* status_out) {
+  ZK_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
+  if (batch == 0 || batch > pk->max_batch) {
+    ctx->err = "plonk: batch must be in [1, max_batch]";
+    return ZKMI_ERR_ARG;
+  }
+  const size_t n = (size_t)1 << pk->log_n, m = 4 * n, Bp = round_up(batch, 64);
+  if (cs->n_constraints > n || cs->n_public - 1 != pk->n_public) {
+    ctx->err = "plonk: constraint system does not match the key";
+    return ZKMI_ERR_ARG;
+  }
+  if ((rc = round1_begin(ctx, pk, batch))) return rc;
+  const size_t n_in = cs->n_public - 1 + cs->n_secret, nc = cs->n_constraints;
+  // stage inputs + blinding scalars (host or device, proof-major)
+  // value file and gate columns: big[0] = slots (reused later), big[1..3] = a, b, c; every size is
+  // checked before anything is staged
+  if ((size_t)cs->n_slots > m || n_in > m) {
+    ctx->err = "plonk: value file or input vector larger than the 4n work buffer";
+    return ZKMI_ERR_ARG;
+  }
+  RoundTmp tin(ctx), tbl(ctx);
+  if ((rc = tin.alloc(batch * n_in * 32)) || (rc = tbl.alloc(batch * 9 * 32))) return rc;
+  void *in_dev = tin.p, *bl_dev = tbl.p;
+  ZK_HIP(hipMemcpyAsync(in_dev, inputs, batch * n_in * 32, hipMemcpyDefault, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(bl_dev, blind, batch * 9 * 32, hipMemcpyDefault, ctx->stream));
+  Fr* slots = (Fr*)pk->big[0].p;
+  Fr *A = (Fr*)pk->big[1].p, *B = (Fr*)pk->big[2].p, *C = (Fr*)pk->big[3].p;
+  void* st;
+  if ((rc = ensure_scratch(ctx, ctx->sets[0].misc, Bp * 4, &st))) return rc;
+  rc = transpose_in(ctx, in_dev, slots + Bp, n_in, batch, Bp, 32);
+  // the inputs in gnark's image, for PI(X) in round 3: big[5] rows 0 .. n_pub - 1 are the public ones
+  if (!rc) rc = transpose_in(ctx, in_dev, pk->big[5].p, n_in, batch, Bp, 32);
+  if (!rc) rc = rows_to_f_domain(ctx, slots + Bp, n_in, Bp);
+  if (!rc) rc = transpose_in(ctx, bl_dev, pk->small[0].p, 9, batch, Bp, 32);
+  if (!rc) rc = solve_bi(ctx, cs, slots, A, B, C, (int32_t*)st, Bp);
+  if (!rc) rc = rows_to_std_domain(ctx, A, nc, Bp);
+  if (!rc) rc = rows_to_std_domain(ctx, B, nc, Bp);
+  if (!rc) rc = rows_to_std_domain(ctx, C, nc, Bp);
+  hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  ZK_HIP(hipMemcpy(status_out, st, batch * 4, hipMemcpyDefault));
+  return round1_tail(ctx, pk, nc, commits_out);
 }
 
 // Round 2: beta, gamma (batch x 2 fr) -> grand product z, blinded, commitment [z].
@@ -903,27 +1019,15 @@ Fr fr_u64(uint64_t v) {
 
 extern "C" {
 
-/* proofs_out: batch x 96 words of 8 bytes = 9 G1 affine points ([a] [b] [c] [z] [t_lo] [t_mid] [t_hi]
- * [W_zeta] [W_zeta_w], Montgomery) then 6 fr (a, b, c, S1, S2 at zeta, z at zeta w; Montgomery). */
-int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
-                     size_t batch, const void* blind, const uint8_t* vk_digest /* 32 bytes */,
-                     void* proofs_out, int32_t* status_out) {
-  if (!ctx || !pk || !cs || !inputs || !blind || !vk_digest || !proofs_out || !status_out || batch == 0)
-    return ZKMI_ERR_ARG;
+// Rounds 2 .. 5 with the transcript between them, after either round 1: pubs = batch x n_public public
+// inputs (gnark's image, host), abc = the commitments of round 1; assembles the records
+static int prove_after_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch, const std::vector<Fr>& pubs,
+                              const std::vector<G1Affine>& abc, const uint8_t* vk_digest,
+                              void* proofs_out) {
   const size_t n = (size_t)1 << pk->log_n, n_pub = pk->n_public;
-  const size_t n_in = cs->n_public - 1 + cs->n_secret;
-  // public inputs on the host (gnark's image)
-  std::vector<Fr> pubs(batch * (n_pub ? n_pub : 1));
-  for (size_t p = 0; p < batch && n_pub; p++)
-    if (hipMemcpy(pubs.data() + p * n_pub, (const char*)inputs + p * n_in * 32, n_pub * 32,
-                  hipMemcpyDefault) != hipSuccess) {
-      ctx->err = "plonk_prove: cannot read the public inputs";
-      return ZKMI_ERR_HIP;
-    }
-  std::vector<G1Affine> abc(batch * 3), cz(batch), ct(batch * 3), cw(batch * 2);
+  std::vector<G1Affine> cz(batch), ct(batch * 3), cw(batch * 2);
   std::vector<Fr> bg(batch * 2), al(batch), zz(batch * 2), ev(batch * 6), sc(batch * 14);
-  int rc = zkmi_plonk_round1(ctx, pk, cs, inputs, batch, blind, abc.data(), status_out);
-  if (rc) return rc;
+  int rc;
   for (size_t p = 0; p < batch; p++) {
     Transcript t("gamma");
     t.h.update(vk_digest, 32);
@@ -1034,6 +1138,318 @@ int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const 
   }
   ZK_HIP(hipMemcpy(proofs_out, rec.data(), rec.size(), hipMemcpyDefault));
   return ZKMI_OK;
+}
+
+/* proofs_out: batch x 96 words of 8 bytes = 9 G1 affine points ([a] [b] [c] [z] [t_lo] [t_mid] [t_hi]
+ * [W_zeta] [W_zeta_w], Montgomery) then 6 fr (a, b, c, S1, S2 at zeta, z at zeta w; Montgomery). */
+int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
+                     size_t batch, const void* blind, const uint8_t* vk_digest /* 32 bytes */,
+                     void* proofs_out, int32_t* status_out) {
+  if (!ctx || !pk || !cs || !inputs || !blind || !vk_digest || !proofs_out || !status_out || batch == 0)
+    return ZKMI_ERR_ARG;
+  const size_t n_pub = pk->n_public;
+  const size_t n_in = cs->n_public - 1 + cs->n_secret;
+  // public inputs on the host (gnark's image)
+  std::vector<Fr> pubs(batch * (n_pub ? n_pub : 1));
+  for (size_t p = 0; p < batch && n_pub; p++)
+    if (hipMemcpy(pubs.data() + p * n_pub, (const char*)inputs + p * n_in * 32, n_pub * 32,
+                  hipMemcpyDefault) != hipSuccess) {
+      ctx->err = "plonk_prove: cannot read the public inputs";
+      return ZKMI_ERR_HIP;
+    }
+  std::vector<G1Affine> abc(batch * 3);
+  int rc = zkmi_plonk_round1(ctx, pk, cs, inputs, batch, blind, abc.data(), status_out);
+  if (rc) return rc;
+  return prove_after_round1(ctx, pk, batch, pubs, abc, vk_digest, proofs_out);
+}
+
+// ---- the gnark drop-in entry: key from the trace form, round 1 from solved witnesses ----------------
+// The seven arrays zkmi_plonk_pk_load takes as data, computed here in gnark's image: the powers and
+// the sigma lookup by the kernels above; the eight polynomials (five selectors, three sigma columns)
+// as eight lanes of one batch-inner matrix of 64: inverse transform on the domain, then the coset
+// transform on 5 <w_4n> that round 3 runs for the wire polynomials, each transposed back out to the
+// poly-major arrays the kernels read wave-uniformly.
+static int pk_from_trace(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_plonk_trace_desc* d) {
+  const size_t n = (size_t)1 << pk->log_n, m = 4 * n, Bp = 64;
+  if (!d->selectors || !d->perm) {
+    ctx->err = "plonk trace: selectors and perm must not be null";
+    return ZKMI_ERR_ARG;
+  }
+  pk->perm.resize(3 * n);
+  ZK_HIP(hipMemcpy(pk->perm.data(), d->perm, 3 * n * 4, hipMemcpyDefault));
+  const std::string bad = scs_perm_validate(pk->perm.data(), n);
+  if (!bad.empty()) {
+    ctx->err = bad;
+    return ZKMI_ERR_ARG;
+  }
+  int rc;
+  NttPlan *plan_n, *plan_m;
+  if ((rc = get_plan(ctx, (int)pk->log_n, &plan_n)) ||
+      (rc = get_plan(ctx, (int)pk->log_n + 2, &plan_m)))
+    return rc;
+  struct { Fr** dst; size_t count; } arr[7] = {{&pk->coef, 8 * n}, {&pk->coset, 8 * m},
+                                               {&pk->sigma, 3 * n}, {&pk->omega, n},
+                                               {&pk->coset_x, m},   {&pk->l1, m},
+                                               {&pk->zh_inv, 4}};
+  for (auto& a : arr)
+    if (hipMalloc((void**)a.dst, a.count * 32) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "plonk trace: hipMalloc(" + std::to_string(a.count * 32) + " B) failed";
+      return ZKMI_ERR_OOM;
+    }
+  // temporaries: the permutation, the eight Lagrange columns poly-major, and the two matrices the
+  // transforms alternate between (n rows; 4n rows, which first holds the n rows going in)
+  RoundTmp perm_dev(ctx), lag(ctx), mat_n(ctx), mat_m(ctx);
+  if ((rc = perm_dev.alloc(3 * n * 4)) || (rc = lag.alloc(8 * n * 32)) ||
+      (rc = mat_n.alloc(n * Bp * 32)) || (rc = mat_m.alloc(m * Bp * 32)))
+    return rc;
+  // generators of the two domains, from the plans' twiddle tables (w^i, i < n / 2; n >= 16)
+  Fr w, w4;
+  ZK_HIP(hipMemcpy(&w, plan_n->tw_fwd + 1, 32, hipMemcpyDeviceToHost));
+  ZK_HIP(hipMemcpy(&w4, plan_m->tw_fwd + 1, 32, hipMemcpyDeviceToHost));
+  const auto grid = [](size_t count) { return dim3((unsigned)((count + 255) / 256)); };
+  hipLaunchKernelGGL(plonk_powers_kernel, grid(n), dim3(256), 0, ctx->stream, pk->omega, n, w,
+                     Fr::one());
+  hipLaunchKernelGGL(plonk_powers_kernel, grid(m), dim3(256), 0, ctx->stream, pk->coset_x, m, w4,
+                     fr_small(5));
+  ZK_HIP(hipMemcpyAsync(perm_dev.p, pk->perm.data(), 3 * n * 4, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(plonk_sigma_kernel, grid(3 * n), dim3(256), 0, ctx->stream,
+                     (const uint32_t*)perm_dev.p, (const Fr*)pk->omega, pk->sigma, pk->log_n,
+                     fr_small(5), fr_small(25));
+  ZK_HIP(hipGetLastError());
+  Fr* lg = (Fr*)lag.p;
+  ZK_HIP(hipMemcpyAsync(lg, d->selectors, 5 * n * 32, hipMemcpyDefault, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(lg + 5 * n, pk->sigma, 3 * n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+  Fr *Mn = (Fr*)mat_n.p, *Mm = (Fr*)mat_m.p;
+  if ((rc = transpose_in(ctx, lg, Mm, n, 8, Bp, 32)) ||
+      (rc = ntt_bi(ctx, plan_n, Mm, Mn, Bp, true, false, n)) ||
+      (rc = transpose_out(ctx, Mn, pk->coef, n, 8, Bp, 32)) ||
+      (rc = ntt_bi(ctx, plan_m, Mn, Mm, Bp, false, true, n)) ||
+      (rc = transpose_out(ctx, Mm, pk->coset, m, 8, Bp, 32)))
+    return rc;
+  // Z_H on the coset: x_j^n - 1 = 5^n i^j - 1 with i = w_4n^n, period 4; L_1 from it
+  const Fr ninv = inverse(fr_u64(n)), i4 = fr_pow_u64(w4, n);
+  Fr4 zh_n;
+  Fr zh_inv[4], t = fr_pow_u64(fr_small(5), n);
+  for (int k = 0; k < 4; k++) {
+    const Fr zh = sub(t, Fr::one());
+    zh_inv[k] = inverse(zh);
+    zh_n.v[k] = mul(zh, ninv);
+    t = mul(t, i4);
+  }
+  ZK_HIP(hipMemcpyAsync(pk->zh_inv, zh_inv, sizeof zh_inv, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(plonk_l1_kernel, grid(m), dim3(256), 0, ctx->stream, (const Fr*)pk->coset_x,
+                     pk->l1, m, zh_n);
+  ZK_HIP(hipGetLastError());
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  return ZKMI_OK;
+}
+
+int zkmi_plonk_pk_load_trace(zkmi_ctx* ctx, const zkmi_plonk_trace_desc* d, zkmi_plonk_pk** out) {
+  ZK_HIP(hipSetDevice(ctx->device));
+  if (!d || !out) return ZKMI_ERR_ARG;
+  zkmi_plonk_pk* pk;
+  int rc = pk_new(ctx, d->log_n, d->n_public, d->max_batch, &pk);
+  if (rc) return rc;
+  if ((rc = require_idle(ctx)) || (rc = pk_from_trace(ctx, pk, d)) ||
+      (rc = pk_finish(ctx, pk, PkCommon{d->srs_g1, d->window_bits, d->lag_g1, d->lag_rows, d->lag_k}))) {
+    zkmi_plonk_pk_free(ctx, pk);
+    return rc;
+  }
+  *out = pk;
+  return ZKMI_OK;
+}
+
+void zkmi_scs_free(zkmi_ctx* ctx, zkmi_scs* scs) {
+  if (!scs) return;
+  if (ctx) {
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+  }
+  for (uint32_t* p : scs->x)
+    if (p) hipFree(p);
+  if (scs->marks) hipFree(scs->marks);
+  if (scs->sel) hipFree(scs->sel);
+  delete scs;
+}
+
+int zkmi_scs_load(zkmi_ctx* ctx, const zkmi_scs_desc* d, zkmi_scs** out) {
+  ZK_HIP(hipSetDevice(ctx->device));
+  if (!d || !out) return ZKMI_ERR_ARG;
+  *out = nullptr;
+  const ScsShape shape{d->n_wires, d->n_gates, d->n_public};
+  // the counts and the pointers before anything is sized or read by them
+  std::string bad = !d->xa || !d->xb || !d->xc || !d->selectors
+                        ? std::string("scs: xa, xb, xc and selectors must not be null")
+                        : scs_shape_check(shape);
+  if (!bad.empty()) {
+    ctx->err = bad;
+    return ZKMI_ERR_ARG;
+  }
+  const size_t ng = d->n_gates;
+  auto* s = new zkmi_scs();
+  s->n_wires = d->n_wires;
+  s->n_gates = d->n_gates;
+  s->n_public = d->n_public;
+  const uint32_t* src[3] = {d->xa, d->xb, d->xc};
+  std::vector<Fr> sel(5 * ng);
+  std::vector<uint32_t> marks(ng);
+  bool ok = hipMemcpy(sel.data(), d->selectors, 5 * ng * 32, hipMemcpyDefault) == hipSuccess;
+  for (int c = 0; ok && c < 3; c++) {
+    s->hx[c].resize(ng);
+    ok = hipMemcpy(s->hx[c].data(), src[c], ng * 4, hipMemcpyDefault) == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    ctx->err = "scs: cannot read the system";
+    zkmi_scs_free(ctx, s);
+    return ZKMI_ERR_HIP;
+  }
+  // every wire index is range-checked here, before a kernel can use it as an address
+  bad = scs_validate(shape, s->hx[0].data(), s->hx[1].data(), s->hx[2].data(), sel.data(),
+                     marks.data());
+  if (!bad.empty()) {
+    ctx->err = bad;
+    zkmi_scs_free(ctx, s);
+    return ZKMI_ERR_ARG;
+  }
+  for (size_t i = 0; i < 4 * ng; i++) sel[i] = lift(sel[i], 5);   // qL qR qO qM: 2^261 images
+  for (int c = 0; ok && c < 3; c++)
+    ok = hipMalloc((void**)&s->x[c], ng * 4) == hipSuccess &&
+         hipMemcpy(s->x[c], s->hx[c].data(), ng * 4, hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && hipMalloc((void**)&s->marks, ng * 4) == hipSuccess &&
+       hipMemcpy(s->marks, marks.data(), ng * 4, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMalloc((void**)&s->sel, 5 * ng * 32) == hipSuccess &&
+       hipMemcpy(s->sel, sel.data(), 5 * ng * 32, hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    ctx->err = "scs: device upload failed";
+    zkmi_scs_free(ctx, s);
+    return ZKMI_ERR_HIP;
+  }
+  *out = s;
+  return ZKMI_OK;
+}
+
+int zkmi_plonk_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
+                              const void* wires, const void* a, const void* b, const void* c,
+                              size_t n_gates, size_t batch, const void* blind, void* commits_out,
+                              int32_t* status_out) {
+  ZK_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
+  if (!pk || !blind || !commits_out || !status_out) {
+    ctx->err = "plonk witness: null argument";
+    return ZKMI_ERR_ARG;
+  }
+  if (batch == 0 || batch > pk->max_batch) {
+    ctx->err = "plonk: batch must be in [1, max_batch]";
+    return ZKMI_ERR_ARG;
+  }
+  const bool wire_form = scs && wires && !a && !b && !c;
+  const bool column_form = !scs && !wires && a && b && c;
+  if (!wire_form && !column_form) {
+    ctx->err = "plonk witness: give either a system and its wires (a = b = c = NULL) or the three "
+               "columns a, b, c (scs = wires = NULL)";
+    return ZKMI_ERR_ARG;
+  }
+  const size_t n = (size_t)1 << pk->log_n, m = 4 * n, n_pub = pk->n_public;
+  if (scs) {
+    if (n_gates && n_gates != scs->n_gates) {
+      ctx->err = "plonk witness: n_gates differs from the loaded system's";
+      return ZKMI_ERR_ARG;
+    }
+    n_gates = scs->n_gates;
+  }
+  if (n_gates == 0 || n_gates > n) {
+    ctx->err = "plonk witness: n_gates must be in [1, 2^log_n], the key's domain";
+    return ZKMI_ERR_ARG;
+  }
+  if (scs ? scs->n_public != n_pub : n_gates < n_pub) {
+    ctx->err = scs ? "plonk witness: the system has " + std::to_string(scs->n_public) +
+                         " public inputs, the key " + std::to_string(n_pub)
+                   : std::string("plonk witness: fewer gate rows than the key has public inputs");
+    return ZKMI_ERR_ARG;
+  }
+  if (scs && scs->n_wires > m) {
+    ctx->err = "plonk witness: wire vector larger than the 4n work buffer";
+    return ZKMI_ERR_ARG;
+  }
+  // first prove of this (trace-loaded key, system) pair: the wiring against the key's permutation
+  if (scs && !pk->perm.empty() && scs->checked_key != pk->serial) {
+    const std::string bad =
+        scs_wiring_check(ScsShape{scs->n_wires, scs->n_gates, scs->n_public}, scs->hx[0].data(),
+                         scs->hx[1].data(), scs->hx[2].data(), pk->perm.data(), n);
+    if (!bad.empty()) {
+      ctx->err = bad;
+      return ZKMI_ERR_ARG;
+    }
+    scs->checked_key = pk->serial;
+  }
+  if ((rc = round1_begin(ctx, pk, batch))) return rc;
+  const size_t Bp = pk->Bp;
+  RoundTmp tbl(ctx);
+  if ((rc = tbl.alloc(batch * 9 * 32))) return rc;
+  ZK_HIP(hipMemcpyAsync(tbl.p, blind, batch * 9 * 32, hipMemcpyDefault, ctx->stream));
+  void* st;
+  if ((rc = ensure_scratch(ctx, ctx->sets[0].misc, Bp * 4, &st))) return rc;
+  ZK_HIP(hipMemsetAsync(st, 0, Bp * 4, ctx->stream));
+  Fr *W = (Fr*)pk->big[0].p, *A = (Fr*)pk->big[1].p, *B = (Fr*)pk->big[2].p, *C = (Fr*)pk->big[3].p;
+  Fr* pub = (Fr*)pk->big[5].p;   // rows 0 .. n_pub - 1: the public inputs, for PI(X) in round 3
+  rc = transpose_in(ctx, tbl.p, pk->small[0].p, 9, batch, Bp, 32);
+  if (!rc && scs) {
+    rc = stage_rows(ctx, wires, scs->n_wires, batch, Bp, W);
+    if (!rc) {
+      const ScsDev dev{{scs->x[0], scs->x[1], scs->x[2]}, scs->marks, scs->sel, scs->n_gates,
+                       scs->n_public};
+      hipLaunchKernelGGL(scs_gate_kernel,
+                         dim3((unsigned)(Bp / 64), (unsigned)std::min<size_t>((n_gates + 3) / 4, 32768)),
+                         dim3(256), 0, ctx->stream, dev, (const Fr*)W, A, B, C, pub, (int32_t*)st, Bp);
+      if (hipGetLastError() != hipSuccess) rc = ZKMI_ERR_HIP;
+    }
+  } else if (!rc) {
+    rc = stage_rows(ctx, a, n_gates, batch, Bp, A);
+    if (!rc) rc = stage_rows(ctx, b, n_gates, batch, Bp, B);
+    if (!rc) rc = stage_rows(ctx, c, n_gates, batch, Bp, C);
+    if (!rc && n_pub &&
+        hipMemcpyAsync(pub, A, n_pub * Bp * 32, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+      rc = ZKMI_ERR_HIP;
+  }
+  // the caller's arrays have been consumed once the stream has passed the copies
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = ZKMI_ERR_HIP;
+  if (rc) {
+    if (rc == ZKMI_ERR_HIP && ctx->err.empty()) ctx->err = "plonk witness: HIP error while staging";
+    return rc;
+  }
+  ZK_HIP(hipMemcpy(status_out, st, batch * 4, hipMemcpyDefault));
+  return round1_tail(ctx, pk, n_gates, commits_out);
+}
+
+int zkmi_plonk_prove_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
+                             const void* wires, const void* a, const void* b, const void* c,
+                             size_t n_gates, size_t batch, const void* blind,
+                             const uint8_t* vk_digest, void* proofs_out, int32_t* status_out) {
+  if (!ctx) return ZKMI_ERR_ARG;
+  if (!pk || !blind || !vk_digest || !proofs_out || !status_out || batch == 0) {
+    ctx->err = "plonk_prove_witness: null argument or empty batch";
+    return ZKMI_ERR_ARG;
+  }
+  std::vector<G1Affine> abc(batch * 3);
+  int rc = zkmi_plonk_round1_witness(ctx, pk, scs, wires, a, b, c, n_gates, batch, blind, abc.data(),
+                                     status_out);
+  if (rc) return rc;
+  // public inputs: column a of rows 0 .. n_public - 1, which round 1 left in big[5]
+  const size_t n_pub = pk->n_public;
+  std::vector<Fr> pubs(batch * (n_pub ? n_pub : 1));
+  if (n_pub) {
+    RoundTmp t(ctx);
+    if ((rc = t.alloc(batch * n_pub * 32)) ||
+        (rc = transpose_out(ctx, pk->big[5].p, t.p, n_pub, batch, pk->Bp, 32)))
+      return rc;
+    ZK_HIP(hipMemcpyAsync(pubs.data(), t.p, batch * n_pub * 32, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return prove_after_round1(ctx, pk, batch, pubs, abc, vk_digest, proofs_out);
 }
 
 }  // extern "C"

@@ -133,7 +133,7 @@ static void parallel_copy(void* dst, const void* src, size_t bytes, int threads)
 // One proof-major caller array [batch][rows] (host pageable, host pinned or device) -> batch-inner
 // rows of `dst` on ctx->stream.  Pageable memory has been consumed when this returns; pinned and
 // device memory must stay valid until the stream has passed the copies (the matching collect).
-static int stage_rows(zkmi_ctx* ctx, const void* src, size_t rows, size_t batch, size_t Bp, void* dst) {
+int stage_rows(zkmi_ctx* ctx, const void* src, size_t rows, size_t batch, size_t Bp, void* dst) {
   if (rows == 0) return ZKMI_OK;
   const int kind = pointer_kind(src);
   if (kind == PTR_DEVICE) return transpose_tile(ctx, src, dst, rows, batch, 0, Bp);

@@ -224,6 +224,16 @@ struct zkmi_r1cs {
   zk::Fr* coeffs = nullptr;   // device, 2^261 images (gnark's Montgomery image times 2^5: fmul_261)
 };
 
+// the sparse constraint system of zkmi_scs_load (plonk.hip; checks: scs_check.h)
+struct zkmi_scs {
+  uint32_t n_wires = 0, n_gates = 0, n_public = 0;
+  uint32_t* x[3] = {};         // device, n_gates wire indices each: columns a, b, c
+  uint32_t* marks = nullptr;   // device, n_gates words: scs_check.h marks of the five selectors
+  zk::Fr* sel = nullptr;       // device, 5 x n_gates: qL qR qO qM as 2^261 images, qC as loaded
+  std::vector<uint32_t> hx[3]; // host copies, for the wiring check against a key's permutation
+  mutable uint64_t checked_key = 0;   // serial of the trace-loaded key the wiring was last checked against
+};
+
 namespace zk {
 
 #if defined(__HIPCC__)
@@ -273,6 +283,10 @@ int require_idle(zkmi_ctx* ctx);
 enum { PTR_PAGEABLE = 0, PTR_PINNED = 1, PTR_DEVICE = 2 };
 int pointer_kind(const void* p);
 void witness_ring_free(zkmi_ctx* ctx);
+// witness.hip: one proof-major caller array [batch][rows] of fr (pageable, page-locked or device
+// memory) -> batch-inner rows of `dst` on ctx->stream, host memory through the context's pinned ring.
+// Pageable memory has been consumed on return; the rest when the stream has passed the copies.
+int stage_rows(zkmi_ctx* ctx, const void* src, size_t rows, size_t batch, size_t Bp, void* dst);
 
 // RAII staging of a caller buffer (host or device) as device memory
 struct Staged {

@@ -174,6 +174,38 @@ class ScsCircuit:
                                            dtype=np.uint32))
             self.n_nonbit_rows = max(getattr(self, "n_nonbit_rows", 0), len(head))
 
+    def wiring(self):
+        """(xa, xb, xc, n_wires): the wire every gate reads in columns a, b, c (uint32 [n_gates]
+        each), what zkmi_scs_desc takes and what a shim reads off gnark's SparseR1CS.  The wires are
+        the SSA values the gates touch, renumbered densely: ONE stays 0, the public inputs stay
+        1 .. n_public - 1, the rest follow in the order of their SSA ids."""
+        if getattr(self, "_wiring", None) is None:
+            n_pub = self.n_public - 1
+            rest = sorted({v for col in self.wires for v in col if v > n_pub})
+            wire_of = {v: v for v in range(n_pub + 1)}
+            wire_of.update({v: n_pub + 1 + i for i, v in enumerate(rest)})
+            cols = [np.array([wire_of[v] for v in col], dtype=np.uint32) for col in self.wires]
+            self._wiring = (cols[0], cols[1], cols[2], n_pub + 1 + len(rest))
+        return self._wiring
+
+    def wire_vectors(self, a, b, c):
+        """Solved columns -> the wire vectors zkmi_plonk_prove_witness takes (scs != NULL form): wire
+        w gets the value of a position that reads it.  a, b, c: [batch, n_gates, 4] uint64 arrays
+        (Montgomery image) -> [batch, n_wires, 4]; or, per proof, lists of n_gates integers -> lists
+        of n_wires integers."""
+        xa, xb, xc, n_wires = self.wiring()
+        if isinstance(a, np.ndarray) and a.ndim == 3:
+            out = np.zeros((a.shape[0], n_wires, 4), dtype=np.uint64)
+            for x, col in ((xa, a), (xb, b), (xc, c)):
+                out[:, x] = col[:, :self.n_gates]
+            return out
+        out = [[0] * n_wires for _ in a]
+        for x, col in ((xa, a), (xb, b), (xc, c)):
+            for w, vals in zip(out, col):
+                for g, xw in enumerate(x.tolist()):
+                    w[xw] = vals[g]
+        return out
+
     def is_satisfied(self, a, b, c, public):
         """gate equations + copy constraints on full columns (lists of ints, length n_gates)."""
         g = self.gates

@@ -62,6 +62,19 @@ class R1csSolverDesc(C.Structure):
                 ("lanes_per_proof", C.c_uint32), ("hint_set", C.c_uint32)]
 
 
+class PlonkTraceDesc(C.Structure):
+    _fields_ = [("log_n", C.c_uint32), ("n_public", C.c_uint32), ("selectors", C.c_void_p),
+                ("perm", C.c_void_p), ("srs_g1", C.c_void_p), ("window_bits", C.c_uint32),
+                ("max_batch", C.c_uint32), ("lag_g1", C.c_void_p * 3), ("lag_rows", C.c_void_p * 3),
+                ("lag_k", C.c_uint32)]
+
+
+class ScsDesc(C.Structure):
+    _fields_ = [("n_wires", C.c_uint32), ("n_gates", C.c_uint32), ("n_public", C.c_uint32),
+                ("xa", C.c_void_p), ("xb", C.c_void_p), ("xc", C.c_void_p),
+                ("selectors", C.c_void_p)]
+
+
 HINTS_BASIC, HINTS_STD, HINTS_EMULATED = 0, 1, 3      # enum zkmi_hint_set (2 alone is not a set)
 
 
@@ -121,6 +134,11 @@ SYMBOLS = [
     ("zkmi_plonk_round4", _I, [_P, _P, _P, _P]),
     ("zkmi_plonk_round5", _I, [_P, _P, _P, _P]),
     ("zkmi_plonk_prove", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
+    ("zkmi_plonk_pk_load_trace", _I, [_P, C.POINTER(PlonkTraceDesc), C.POINTER(_P)]),
+    ("zkmi_scs_load", _I, [_P, C.POINTER(ScsDesc), C.POINTER(_P)]),
+    ("zkmi_scs_free", None, [_P, _P]),
+    ("zkmi_plonk_round1_witness", _I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _P]),
+    ("zkmi_plonk_prove_witness", _I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P]),
 ]
 
 _lib = None
@@ -386,6 +404,20 @@ class Context:
     def prove_r1cs_submit(self, pk_h, solver_h, inputs, batch, rs):
         self._check(self.lib.zkmi_prove_r1cs_submit(self.h, pk_h, solver_h, _ptr(inputs), batch,
                                                     _ptr(rs)), "zkmi_prove_r1cs_submit")
+
+    def plonk_pk_load_trace(self, desc: "PlonkTraceDesc"):
+        h = C.c_void_p()
+        self._check(self.lib.zkmi_plonk_pk_load_trace(self.h, C.byref(desc), C.byref(h)),
+                    "zkmi_plonk_pk_load_trace")
+        return h
+
+    def scs_load(self, desc: "ScsDesc"):
+        h = C.c_void_p()
+        self._check(self.lib.zkmi_scs_load(self.h, C.byref(desc), C.byref(h)), "zkmi_scs_load")
+        return h
+
+    def scs_free(self, h):
+        self.lib.zkmi_scs_free(self.h, h)
 
     def host_alloc(self, shape, dtype=np.uint64):
         """numpy array over page-locked memory from zkmi_host_alloc (free with host_free)."""

@@ -333,61 +333,182 @@ class Prover:
         Returns (list of Proof, status [batch]).  The five rounds one by one with the transcript in
         Python: the reference implementation of the transcript that ``prove_raw`` (C++) is tested
         against."""
-        ctx, lib, pk = self.ctx, self.ctx.lib, self.pk
+        ctx, pk = self.ctx, self.pk
         batch = inputs.shape[0]
         if tuple(inputs.shape) != (batch, self.scs.n_inputs, 4) or tuple(blind.shape) != (batch, 9, 4):
             raise ValueError("inputs must be [batch, n_inputs, 4], blind [batch, 9, 4]")
         inputs, blind = np.ascontiguousarray(inputs), np.ascontiguousarray(blind)
-        n_pub = pk.n_public
         rinv = pow(1 << 256, R - 2, R)
-        pubs = [[v * rinv % R for v in array_to_ints(inputs[i, :n_pub])] for i in range(batch)]
-        pts = lambda arr: [_verify.g1_from_image(arr[i]) for i in range(arr.shape[0])]
+        pubs = [[v * rinv % R for v in array_to_ints(inputs[i, :pk.n_public])] for i in range(batch)]
+
+        def round1(c_abc, status):
+            ctx._check(ctx.lib.zkmi_plonk_round1(ctx.h, self.pk_h, self.cs_h, inputs.ctypes.data,
+                                                 batch, blind.ctypes.data, c_abc.ctypes.data,
+                                                 status.ctypes.data), "zkmi_plonk_round1")
+        return _prove_rounds(ctx, pk, self.pk_h, batch, pubs, round1)
+
+
+def _prove_rounds(ctx, pk, pk_h, batch, pubs, round1):
+    """The five rounds one by one with the transcript in Python, after ``round1(c_abc, status)`` has
+    run either round-1 entry on the key ``pk_h``; pubs: per proof, the public inputs as integers."""
+    lib = ctx.lib
+    pts = lambda arr: [_verify.g1_from_image(arr[i]) for i in range(arr.shape[0])]
+    status = np.zeros(batch, dtype=np.int32)
+    c_abc = np.zeros((batch, 3, 8), dtype=np.uint64)
+    round1(c_abc, status)
+    A, B, Cc = (pts(c_abc[:, k]) for k in range(3))
+    gamma = [challenge("gamma", pk.vk_digest, *pubs[i], A[i], B[i], Cc[i]) for i in range(batch)]
+    beta = [challenge("beta", g) for g in gamma]
+    bg = np.stack([to_mont_array([beta[i], gamma[i]]) for i in range(batch)])
+    c_z = np.zeros((batch, 8), dtype=np.uint64)
+    ctx._check(lib.zkmi_plonk_round2(ctx.h, pk_h, bg.ctypes.data, c_z.ctypes.data),
+               "zkmi_plonk_round2")
+    Z = pts(c_z)
+    alpha = [challenge("alpha", beta[i], Z[i]) for i in range(batch)]
+    al = to_mont_array(alpha)
+    c_t = np.zeros((batch, 3, 8), dtype=np.uint64)
+    ctx._check(lib.zkmi_plonk_round3(ctx.h, pk_h, al.ctypes.data, c_t.ctypes.data),
+               "zkmi_plonk_round3")
+    TL, TM, TH = (pts(c_t[:, k]) for k in range(3))
+    zeta = [challenge("zeta", alpha[i], TL[i], TM[i], TH[i]) for i in range(batch)]
+    w = root_of_unity(pk.log_n)
+    zz = np.stack([to_mont_array([z, z * w % R]) for z in zeta])
+    ev_arr = np.zeros((batch, 6, 4), dtype=np.uint64)
+    ctx._check(lib.zkmi_plonk_round4(ctx.h, pk_h, zz.ctypes.data, ev_arr.ctypes.data),
+               "zkmi_plonk_round4")
+    rinv = pow(1 << 256, R - 2, R)
+    evs = [tuple(v * rinv % R for v in array_to_ints(ev_arr[i])) for i in range(batch)]
+    rows = []
+    for i in range(batch):
+        v = challenge("v", zeta[i], *evs[i])
+        sc = lin_scalars(pk, pubs[i], beta[i], gamma[i], alpha[i], zeta[i], evs[i])
+        c0, vp = sc["r0"], 1
+        for e in evs[i][:5]:
+            vp = vp * v % R
+            c0 = (c0 - vp * e) % R
+        rows.append(to_mont_array([sc["qm"], sc["ql"], sc["qr"], sc["qo"], sc["s3"], sc["z"],
+                                   sc["tlo"], sc["tmid"], sc["thi"], c0, v, zeta[i],
+                                   zeta[i] * w % R, evs[i][5]]))
+    sc_arr = np.stack(rows)
+    c_w = np.zeros((batch, 2, 8), dtype=np.uint64)
+    ctx._check(lib.zkmi_plonk_round5(ctx.h, pk_h, sc_arr.ctypes.data, c_w.ctypes.data),
+               "zkmi_plonk_round5")
+    WZ, WZW = pts(c_w[:, 0]), pts(c_w[:, 1])
+    proofs = [Proof(a=A[i], b=B[i], c=Cc[i], z=Z[i], tlo=TL[i], tmid=TM[i], thi=TH[i],
+                    wz=WZ[i], wzw=WZW[i], ev=evs[i]) for i in range(batch)]
+    return proofs, status
+
+
+class WitnessProver:
+    """plonk.Prove from SOLVED witnesses, the way a gnark caller has them: the key loaded from its
+    trace form (zkmi_plonk_pk_load_trace: selector values on the domain and the permutation; the
+    GPU computes the rest), the system as wiring and selectors (zkmi_scs_load), the witnesses as
+    wire vectors or as the three columns (zkmi_plonk_prove_witness).
+
+    ``system``: anything with ``log_n``, ``n_public`` (counting ONE, as ScsCircuit does),
+    ``wiring()`` -> (xa, xb, xc, n_wires), the selector columns ``qL qR qO qM qC`` on the domain,
+    ``sigma`` (3n positions) and, for ``lagrange``, ``lag_order`` -- a frontend/scs.py ScsCircuit,
+    or what a shim reads off gnark's SparseR1CS and plonk.ProvingKey trace.  ``pk``: SRS, vk digest
+    and commitments (``setup``); its expanded arrays are not used."""
+
+    def __init__(self, ctx: _lib.Context, system, pk: ProvingKey, window_bits: int = 0,
+                 max_batch: int = 64, lagrange=None):
+        self.ctx, self.system, self.pk = ctx, system, pk
+        n = 1 << system.log_n
+        if system.log_n != pk.log_n or system.n_public - 1 != pk.n_public:
+            raise ValueError("system and key disagree on log_n / n_public")
+        if lagrange is None:
+            lagrange = system.n_nonbit_rows * 5 <= 2 * n and system.log_n >= 10
+        self.lagrange = bool(lagrange) and pk.srs_lagrange is not None
+        xa, xb, xc, self.n_wires = system.wiring()
+        self.n_gates = len(xa)
+        sel = np.stack([to_mont_array([int(v) % R for v in col])
+                        for col in (system.qL, system.qR, system.qO, system.qM, system.qC)])
+        perm = np.ascontiguousarray(system.sigma, dtype=np.uint32)
+        srs = np.ascontiguousarray(pk.srs_g1)
+        self._keep = [sel, perm, srs]
+        lag_g1, lag_rows, lag_k = (C.c_void_p * 3)(), (C.c_void_p * 3)(), 0
+        if self.lagrange:
+            lag_k = 10
+            for c in range(3):
+                order = np.concatenate([np.array([n, n + 1], dtype=np.uint32), system.lag_order[c]])
+                pts = np.ascontiguousarray(pk.srs_lagrange[order])
+                self._keep += [order, pts]
+                lag_g1[c] = pts.ctypes.data
+                lag_rows[c] = order.ctypes.data
+        self.pk_h = self.scs_h = None
+        self.pk_h = ctx.plonk_pk_load_trace(_lib.PlonkTraceDesc(
+            pk.log_n, pk.n_public, sel.ctypes.data, perm.ctypes.data, srs.ctypes.data, window_bits,
+            max_batch, lag_g1, lag_rows, lag_k))
+        gsel = np.ascontiguousarray(sel[:, :self.n_gates])
+        xs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (xa, xb, xc)]
+        self.scs_h = ctx.scs_load(_lib.ScsDesc(self.n_wires, self.n_gates, pk.n_public,
+                                               *[x.ctypes.data for x in xs], gsel.ctypes.data))
+
+    def close(self):
+        if getattr(self, "pk_h", None):
+            self.ctx.lib.zkmi_plonk_pk_free(self.ctx.h, self.pk_h)
+            self.pk_h = None
+        if getattr(self, "scs_h", None):
+            self.ctx.scs_free(self.scs_h)
+            self.scs_h = None
+
+    proofs_of = staticmethod(Prover.proofs_of)
+
+    def _args(self, blind, wires, columns):
+        """(batch, the seven witness arguments of the C entry, public inputs as an array)"""
+        if (wires is None) == (columns is None):
+            raise ValueError("give either wires or columns")
+        n_pub = self.pk.n_public
+        host = lambda x: x if isinstance(x, np.ndarray) else x.cpu().numpy()
+        if wires is not None:
+            batch = wires.shape[0]
+            if tuple(wires.shape) != (batch, self.n_wires, 4):
+                raise ValueError("wires must be [batch, n_wires, 4]")
+            xa = self.system.wiring()[0]
+            pubs = host(wires)[:, xa[:n_pub]]
+            wit = (self.scs_h, _lib._ptr(wires), None, None, None, 0)
+        else:
+            a, b, c = columns
+            batch = a.shape[0]
+            if any(tuple(x.shape) != (batch, self.n_gates, 4) for x in (a, b, c)):
+                raise ValueError("columns must be three [batch, n_gates, 4] arrays")
+            pubs = host(a[:, :n_pub])
+            wit = (None, None, _lib._ptr(a), _lib._ptr(b), _lib._ptr(c), self.n_gates)
+        if tuple(blind.shape) != (batch, 9, 4):
+            raise ValueError("blind must be [batch, 9, 4]")
+        return batch, wit, pubs
+
+    def prove_raw(self, blind, wires=None, columns=None):
+        """plonk.Prove through zkmi_plonk_prove_witness.  wires: [batch, n_wires, 4] (Montgomery; a
+        numpy array, pageable or from Context.host_alloc, or a device tensor); or columns = (a, b,
+        c), [batch, n_gates, 4] each, taken as they are.  Returns (records, status) as
+        Prover.prove_raw does."""
+        batch, wit, _ = self._args(blind, wires, columns)
+        blind = np.ascontiguousarray(blind)
+        rec = np.zeros((batch, 96), dtype=np.uint64)
         status = np.zeros(batch, dtype=np.int32)
-        c_abc = np.zeros((batch, 3, 8), dtype=np.uint64)
-        ctx._check(lib.zkmi_plonk_round1(ctx.h, self.pk_h, self.cs_h, inputs.ctypes.data, batch,
-                                         blind.ctypes.data, c_abc.ctypes.data, status.ctypes.data),
-                   "zkmi_plonk_round1")
-        A, B, Cc = (pts(c_abc[:, k]) for k in range(3))
-        gamma = [challenge("gamma", pk.vk_digest, *pubs[i], A[i], B[i], Cc[i]) for i in range(batch)]
-        beta = [challenge("beta", g) for g in gamma]
-        bg = np.stack([to_mont_array([beta[i], gamma[i]]) for i in range(batch)])
-        c_z = np.zeros((batch, 8), dtype=np.uint64)
-        ctx._check(lib.zkmi_plonk_round2(ctx.h, self.pk_h, bg.ctypes.data, c_z.ctypes.data),
-                   "zkmi_plonk_round2")
-        Z = pts(c_z)
-        alpha = [challenge("alpha", beta[i], Z[i]) for i in range(batch)]
-        al = to_mont_array(alpha)
-        c_t = np.zeros((batch, 3, 8), dtype=np.uint64)
-        ctx._check(lib.zkmi_plonk_round3(ctx.h, self.pk_h, al.ctypes.data, c_t.ctypes.data),
-                   "zkmi_plonk_round3")
-        TL, TM, TH = (pts(c_t[:, k]) for k in range(3))
-        zeta = [challenge("zeta", alpha[i], TL[i], TM[i], TH[i]) for i in range(batch)]
-        w = root_of_unity(pk.log_n)
-        zz = np.stack([to_mont_array([z, z * w % R]) for z in zeta])
-        ev_arr = np.zeros((batch, 6, 4), dtype=np.uint64)
-        ctx._check(lib.zkmi_plonk_round4(ctx.h, self.pk_h, zz.ctypes.data, ev_arr.ctypes.data),
-                   "zkmi_plonk_round4")
+        vkd = (C.c_uint8 * 32).from_buffer_copy(self.pk.vk_digest)
+        self.ctx._check(self.ctx.lib.zkmi_plonk_prove_witness(
+            self.ctx.h, self.pk_h, *wit, batch, blind.ctypes.data, vkd, rec.ctypes.data,
+            status.ctypes.data), "zkmi_plonk_prove_witness")
+        return rec, status
+
+    def prove(self, blind, wires=None, columns=None):
+        """The round-by-round twin of prove_raw: zkmi_plonk_round1_witness, then Prover.prove's
+        rounds and Python transcript.  Returns (list of Proof, status)."""
+        ctx = self.ctx
+        batch, wit, pubs = self._args(blind, wires, columns)
+        blind = np.ascontiguousarray(blind)
         rinv = pow(1 << 256, R - 2, R)
-        evs = [tuple(v * rinv % R for v in array_to_ints(ev_arr[i])) for i in range(batch)]
-        rows = []
-        for i in range(batch):
-            v = challenge("v", zeta[i], *evs[i])
-            sc = lin_scalars(pk, pubs[i], beta[i], gamma[i], alpha[i], zeta[i], evs[i])
-            c0, vp = sc["r0"], 1
-            for e in evs[i][:5]:
-                vp = vp * v % R
-                c0 = (c0 - vp * e) % R
-            rows.append(to_mont_array([sc["qm"], sc["ql"], sc["qr"], sc["qo"], sc["s3"], sc["z"],
-                                       sc["tlo"], sc["tmid"], sc["thi"], c0, v, zeta[i],
-                                       zeta[i] * w % R, evs[i][5]]))
-        sc_arr = np.stack(rows)
-        c_w = np.zeros((batch, 2, 8), dtype=np.uint64)
-        ctx._check(lib.zkmi_plonk_round5(ctx.h, self.pk_h, sc_arr.ctypes.data, c_w.ctypes.data),
-                   "zkmi_plonk_round5")
-        WZ, WZW = pts(c_w[:, 0]), pts(c_w[:, 1])
-        proofs = [Proof(a=A[i], b=B[i], c=Cc[i], z=Z[i], tlo=TL[i], tmid=TM[i], thi=TH[i],
-                        wz=WZ[i], wzw=WZW[i], ev=evs[i]) for i in range(batch)]
-        return proofs, status
+        pubs = [[v * rinv % R for v in array_to_ints(np.ascontiguousarray(pubs[i]))]
+                if self.pk.n_public else [] for i in range(batch)]
+
+        def round1(c_abc, status):
+            ctx._check(ctx.lib.zkmi_plonk_round1_witness(
+                ctx.h, self.pk_h, *wit, batch, blind.ctypes.data, c_abc.ctypes.data,
+                status.ctypes.data), "zkmi_plonk_round1_witness")
+        return _prove_rounds(ctx, self.pk, self.pk_h, batch, pubs, round1)
 
 
 def verify(pk: ProvingKey, public, proof: Proof) -> bool:

@@ -539,6 +539,76 @@ int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const 
                      size_t batch, const void* blind, const uint8_t* vk_digest, void* proofs_out,
                      int32_t* status_out);
 
+/* -- the gnark drop-in entry of the PLONK prover --------------------------------------------------- */
+/* For a caller that holds gnark's own objects [UPSTREAM-RECALL]: the proving key as a trace
+ * (plonk.ProvingKey: selector values on the domain and a permutation), a constraint.SparseR1CS, and
+ * solved wires -- no zkmi_cs and no expanded key.  Parity with gnark (gate convention of the public
+ * rows, transcript) is unpinned, as for the rest of the PLONK prover.
+ *
+ * zkmi_plonk_pk_load_trace: the key from its trace form.  Everything else zkmi_plonk_pk_desc takes
+ * as data (w^i, the sigma values, the eight coefficient forms and their coset evaluations, the coset
+ * points, L_1 and 1 / Z_H on the coset) is computed on the GPU at load time; a key loaded this way
+ * proves exactly what the same key loaded through zkmi_plonk_pk_load proves. */
+typedef struct {
+  uint32_t log_n;          /* as zkmi_plonk_pk_desc */
+  uint32_t n_public;       /* as zkmi_plonk_pk_desc */
+  const void* selectors;   /* 5 x n fr: qL, qR, qO, qM, qC as values on the domain (Montgomery); rows
+                              past the last gate are zero */
+  const uint32_t* perm;    /* 3n entries of 32 bits (3n <= 3 * 2^24 fits): position c n + r (column
+                              c = 0, 1, 2 for a, b, c; row r) -> its image position; gnark's trace.S
+                              narrowed from int64.  Must be a bijection of [0, 3n) */
+  const void* srs_g1;      /* the remaining fields: as zkmi_plonk_pk_desc */
+  uint32_t window_bits;
+  uint32_t max_batch;
+  const void* lag_g1[3];
+  const uint32_t* lag_rows[3];
+  uint32_t lag_k;
+} zkmi_plonk_trace_desc;
+/* Refuses, with a message: a perm entry >= 3n, a perm that is not a bijection, and whatever
+ * zkmi_plonk_pk_load refuses.  The key keeps a host copy of perm for the wiring check below; the
+ * caller's arrays (host or device) may be freed afterwards.  Free with zkmi_plonk_pk_free. */
+int zkmi_plonk_pk_load_trace(zkmi_ctx* ctx, const zkmi_plonk_trace_desc* desc, zkmi_plonk_pk** out);
+
+/* The sparse constraint system: gate g reads wire xa[g], xb[g], xc[g] in columns a, b, c and asserts
+ *   qL a + qR b + qO c + qM a b + qC + PI_g = 0,   PI_g = -a_g for g < n_public, else 0
+ * (public input g is the value in column a of row g). */
+typedef struct {
+  uint32_t n_wires, n_gates, n_public; /* n_public <= n_gates <= 2^24 */
+  const uint32_t* xa;                  /* n_gates wire indices each, below n_wires */
+  const uint32_t* xb;
+  const uint32_t* xc;
+  const void* selectors;               /* 5 x n_gates fr: the trace's values, Montgomery, reduced */
+} zkmi_scs_desc;
+typedef struct zkmi_scs zkmi_scs;
+/* Validates every index on the host (csrc/scs_check.h), copies the system to the device; the caller's
+ * arrays (host or device) may be freed afterwards. */
+int zkmi_scs_load(zkmi_ctx* ctx, const zkmi_scs_desc* desc, zkmi_scs** out);
+void zkmi_scs_free(zkmi_ctx* ctx, zkmi_scs* scs);
+
+/* Round 1 from solved witnesses, in the place of zkmi_plonk_round1; rounds 2 .. 5 follow as usual.
+ *   scs != NULL (wire form): wires = batch x scs.n_wires fr (Montgomery, reduced), proof-major,
+ *          16-byte aligned, in pageable, page-locked (zkmi_host_alloc) or device memory; a = b = c =
+ *          NULL; n_gates = 0 or the loaded system's.  The device gathers the three columns, checks
+ *          every gate (per-proof ZKMI_ERR_UNSATISFIED in status_out); the copy constraints hold by
+ *          construction.
+ *   scs == NULL (column form): wires = NULL; a, b, c = batch x n_gates fr each, proof-major, taken
+ *          as they are (status_out = 0); the library pads to the domain.
+ * Giving both forms or neither is ZKMI_ERR_ARG.  Also refused, before anything is staged: n_gates
+ * above 2^log_n, a system whose n_public differs from the key's, batch outside [1, max_batch] and,
+ * for a key loaded from its trace form, a wiring that contradicts the key's permutation (checked on
+ * the host at the first prove of a (key, system) pair; a key from zkmi_plonk_pk_load has no
+ * permutation to compare).  The arrays have been consumed when the call returns. */
+int zkmi_plonk_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
+                              const void* wires, const void* a, const void* b, const void* c,
+                              size_t n_gates, size_t batch, const void* blind, void* commits_out,
+                              int32_t* status_out);
+/* zkmi_plonk_prove from solved witnesses: zkmi_plonk_round1_witness, then the same four rounds and
+ * the same transcript, whose public inputs are the values in column a of rows 0 .. n_public - 1. */
+int zkmi_plonk_prove_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
+                             const void* wires, const void* a, const void* b, const void* c,
+                             size_t n_gates, size_t batch, const void* blind,
+                             const uint8_t* vk_digest, void* proofs_out, int32_t* status_out);
+
 /* Per-stage device time of the last zkmi_prove_collect / zkmi_prove_batch in milliseconds, from
  * HIP events on the library's streams: [0] solve (stage 1, second stream), [1] quotient (NTTs +
  * pointwise; with a folded key the transforms of a and b alone), [2] G1 MSMs, [3] G2 MSM, [4] assembly (third stream; overlaps the next batch's
