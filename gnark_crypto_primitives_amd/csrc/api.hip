@@ -423,7 +423,7 @@ void zkmi_destroy(zkmi_ctx* ctx) {
   for (auto& st : ctx->sets)
     for (DevBuf* b : {&st.slots, &st.a, &st.b, &st.c, &st.misc, &st.sums, &st.commit})
       if (b->p) hipFree(b->p);
-  for (DevBuf* b : {&ctx->ntt_tmp, &ctx->build_tmp, &ctx->msm_digits, &ctx->msm_sint,
+  for (DevBuf* b : {&ctx->ntt_tmp, &ctx->ntt_top, &ctx->build_tmp, &ctx->msm_digits, &ctx->msm_sint,
                     &ctx->msm_rowvar, &ctx->msm_part[0], &ctx->msm_part[1], &ctx->side_part2, &ctx->side_part3})
     if (b->p) hipFree(b->p);
   witness_ring_free(ctx);
@@ -641,8 +641,10 @@ static WinPlan plan_explicit(int wb) {
 // buffers), the NTT scratch, the MSM integer scalars + digits + two partial-sum buffers (with what
 // the MSM tails read beside the sums: lane-0 digits and the list of the uniform groups), the
 // table-build scratch that stays allocated, and a margin for the allocator.
+// The three limb-8 planes of the quotient's transforms (ntt.hip) cost nothing for a folded key,
+// whose sets lend their unused c buffer; an unfolded key's are scratch of the context.
 static double prove_working_set_bytes(uint32_t log_n, size_t n_slots, size_t n_in, size_t max_batch,
-                                      size_t n_msm_max, size_t n_commitments) {
+                                      size_t n_msm_max, size_t n_commitments, bool folded) {
   const size_t Bp = round_up(max_batch ? max_batch : 1024, 64);
   const size_t n = (size_t)1 << log_n;
   const SetBytes sb = prove_set_bytes(n_slots, n, n_in, Bp, Bp);
@@ -656,7 +658,8 @@ static double prove_working_set_bytes(uint32_t log_n, size_t n_slots, size_t n_i
   // device half of the witness entry's staging ring (witness.hip): three chunks of ~64 MB, or of
   // one 64-proof column block of the wire matrix when that is larger (n_in = n_wires here)
   const double ring = 3.0 * std::max(68e6, (double)n_in * 32 * 64);
-  return 2 * set + (double)n * Bp * 32 + digits + sint + partials + ring + 2e9 + 1e9;
+  const double planes = (folded || log_n < 8) ? 0.0 : 3.0 * (double)n * Bp * 4;
+  return 2 * set + (double)n * Bp * 32 + planes + digits + sint + partials + ring + 2e9 + 1e9;
 }
 static double free_hbm_bytes() {
   size_t free_b = 0, total_b = 0;
@@ -1025,7 +1028,7 @@ int zkmi_pk_load_planned(zkmi_ctx* ctx, const zkmi_pk_desc* d, const uint32_t* m
                                     std::max((size_t)n_kb, (size_t)n_zb));
   const size_t n_slots = d->n_slots_hint ? d->n_slots_hint : (size_t)d->n_wires + d->n_wires / 20;
   const double ws = prove_working_set_bytes(d->log_n, n_slots, d->n_wires, pk->max_batch, n_msm_max,
-                                            pk->commits.size());
+                                            pk->commits.size(), pk->folded);
   double usable = free_hbm_bytes() - ws;
   if (usable < 0) usable = 0;
   if (d->table_budget_bytes && (double)d->table_budget_bytes < usable)
@@ -1081,8 +1084,9 @@ int zkmi_pk_load_planned(zkmi_ctx* ctx, const zkmi_pk_desc* d, const uint32_t* m
       relax[i] = false;
     }
   // The wire MSMs read the value file, which the solver leaves in the F image; the quotient MSM
-  // reads h (or the coset evaluations of a folded key), which the NTT leaves in gnark's: sign-
-  // pattern tables are built native to those, so that the digit pass reads both as they are.
+  // reads h, which the NTT leaves in gnark's image, or the coset evaluations of a folded key, which
+  // it leaves in the F image (compute_ab_coset_bi, out_f): sign-pattern tables are built native to
+  // those, so that the digit pass reads all of them as they are.
   // (A batch that enters with gnark-image wires pays one conversion pass per wire MSM.)
   auto load = [&](int group, const void* pts, size_t n, const WinPlan& plan, bool relax,
                   zkmi_msm_bases** out, int image) -> int {
@@ -1101,7 +1105,7 @@ int zkmi_pk_load_planned(zkmi_ctx* ctx, const zkmi_pk_desc* d, const uint32_t* m
       (rc = load(1, fold.folded ? (const void*)fold.k.data() : d->g1_k, n_kb, pm[COMB_MSM_K],
                  relax[COMB_MSM_K], &pk->K, MSM_IMAGE_F)) ||
       (rc = load(1, fold.folded ? (const void*)fold.e.data() : d->g1_z, n_zb, pm[COMB_MSM_Z],
-                 relax[COMB_MSM_Z], &pk->Z, MSM_IMAGE_STD)) ||
+                 relax[COMB_MSM_Z], &pk->Z, fold.folded ? MSM_IMAGE_F : MSM_IMAGE_STD)) ||
       (rc = load(2, d->g2_b, d->n_b, pm[COMB_MSM_B2], relax[COMB_MSM_B2], &pk->B2, MSM_IMAGE_F))) {
     zkmi_pk_free(ctx, pk);
     return rc;
@@ -1357,10 +1361,12 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
   Fr* slots = (Fr*)S.slots.p;
   ZK_HIP(hipStreamWaitEvent(ctx->stream, S.ev1, 0));
   hipEventRecord(S.evq[0], ctx->stream);
-  // h: the quotient's coefficients, or (folded key) the coset evaluations of a b; S.c is not read
+  // h: the quotient's coefficients, or (folded key) the coset evaluations of a b.  There nobody
+  // reads S.c and the set's solve is over (ev1), so its n * Bp * 32 bytes hold the three limb-8
+  // planes of the transforms; an unfolded key's come from the context (ntt_top)
   Fr* h;
   if ((rc = pk->folded ? compute_ab_coset_bi(ctx, plan, (Fr*)S.a.p, (Fr*)S.b.p, (Fr*)t0, Bp,
-                                             S.n_constraints, &h, fd)
+                                             S.n_constraints, &h, fd, (int32_t*)S.c.p, true)
                        : compute_h_bi(ctx, plan, (Fr*)S.a.p, (Fr*)S.b.p, (Fr*)S.c.p, (Fr*)t0, Bp,
                                       S.n_constraints, &h, fd)))
     return rc;
@@ -1392,8 +1398,8 @@ static int enqueue_heavy(zkmi_ctx* ctx, int si) {
                     rv)) ||
       (rc = msm_run(ctx, pk->K, slots, pk->k_wire, Bp, batch, v.sK, fd, d1 ? v.w1[2] : nullptr, q4,
                     rv)) ||
-      (rc = msm_run(ctx, pk->Z, h, nullptr, Bp, batch, v.sZ, false, d1 ? v.w1[3] : nullptr, q4,
-                    nullptr, true))) {
+      (rc = msm_run(ctx, pk->Z, h, nullptr, Bp, batch, v.sZ, pk->folded, d1 ? v.w1[3] : nullptr,
+                    q4, nullptr, true))) {
     ctx->msm_ev_set = -1;
     return rc;
   }

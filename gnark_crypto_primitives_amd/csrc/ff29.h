@@ -17,8 +17,9 @@
 //              normalised values (|limb| < 2^29), or one operand with |limb| < 2^30;
 //              |a * b| < 64 p^2.  Result normalised, value in (-p/2, 3p/2).
 //   add/sub/neg: limb-wise, no normalisation.  norm(): carry propagation.
-// The memory image (tables, kernel outputs) stays 8 x u32: canonical value in [0, p).  Between
-// the passes of one transform chain the NTT keeps a signed image instead (pack_lazy below).
+// The memory image (tables, kernel outputs) stays 8 x u32: canonical value in [0, p).  The MSM's
+// accumulators keep a signed image between kernels instead (pack_lazy below); between the passes of
+// one transform chain the NTT stores the nine limbs as they are (ntt.hip).
 #pragma once
 #include "ff.h"
 
@@ -310,7 +311,7 @@ ZK_HD void pack_canonical(uint32_t w[8], const F29<P>& a) {
 // the limbs are shifted into place and limb 8 (bit 232, the sign carrier, |v[8]| < 2^23) sign-
 // extends through word 7.  For a value in [0, 2^255) it is the plain integer, so unpack_lazy also
 // reads every canonical image.  Only code that unpacks with unpack_lazy may read such a buffer
-// (the transform passes of ntt.hip among themselves); what leaves them is pack_canonical's.
+// (the accumulators of ec29.h between the MSM's kernels); what leaves them is pack_canonical's.
 template <class P>
 ZK_HD void pack_lazy(uint32_t w[8], const F29<P>& a) {
   uint64_t acc = 0;

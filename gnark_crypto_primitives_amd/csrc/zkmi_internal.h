@@ -62,6 +62,7 @@ struct zkmi_ctx {
   // zkmi_destroy.  These run on the main stream only, so consecutive batches queue up behind
   // each other:
   zk::DevBuf ntt_tmp;                // NTT temporary of the quotient
+  zk::DevBuf ntt_top;                // limb-8 planes of the 29-bit transform chains (ntt.hip)
   zk::DevBuf build_tmp;              // table-build inversion scratch; proof-of-knowledge temporary
   zk::DevBuf msm_digits, msm_sint;   // MSM digits, converted scalars (comb_scalars_kernel)
   zk::DevBuf msm_rowvar;             // which value-file rows vary over the batch (enqueue_heavy)
@@ -363,13 +364,17 @@ int ntt_bi(zkmi_ctx* ctx, const NttPlan* plan, const Fr* src, Fr* dst, size_t Bp
            bool coset, size_t n_valid);
 // full quotient: a,b,c batch-inner [n][Bp] (rows >= n_valid zero) -> h in `a_out`; t0,t1 scratch
 // abc_f: a, b, c are in the F domain (solver output); the result h is always in gnark's image
+// top: three planes [n][Bp] of int32 for the limb form of a, b and t0 between the passes (ntt.hip,
+// log_n >= 8); null = the context's own (ntt_top)
 int compute_h_bi(zkmi_ctx* ctx, const NttPlan* plan, Fr* a, Fr* b, Fr* c, Fr* t0, size_t Bp,
-                 size_t n_valid, Fr** h_out, bool abc_f = false);
+                 size_t n_valid, Fr** h_out, bool abc_f = false, int32_t* top = nullptr);
 
-// the quotient of a folded key: the n coset evaluations of a * b in gnark's image, *u_out = b
-// (log_n >= 8; a, b as compute_h_bi's, both overwritten)
+// the quotient of a folded key: the n coset evaluations of a * b in gnark's image, or with out_f
+// in the F domain (x * 2^261, canonical), *u_out = b
+// (log_n >= 8; a, b, top as compute_h_bi's, both overwritten)
 int compute_ab_coset_bi(zkmi_ctx* ctx, const NttPlan* plan, Fr* a, Fr* b, Fr* t0, size_t Bp,
-                        size_t n_valid, Fr** u_out, bool abc_f = false);
+                        size_t n_valid, Fr** u_out, bool abc_f = false, int32_t* top = nullptr,
+                        bool out_f = false);
 
 // quotient_fold.hip: what zkmi_pk_load puts in the place of g1_z, g1_k and k_wire when
 // zkmi_pk_desc.fold_r1cs folds (host copies; the device buffers of the fold are gone on return)
