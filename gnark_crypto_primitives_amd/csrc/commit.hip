@@ -155,6 +155,18 @@ __global__ __launch_bounds__(64) void xyzz_add_kernel(G1XYZZ* acc, const G1XYZZ*
 
 namespace zk {
 
+// G1Affine.Marshal(): x || y big-endian, the point at infinity as the flag byte 0x40 and zeros
+void g1_marshal(uint8_t out[64], const G1Affine& d) {
+  if (d.x.is_zero() && d.y.is_zero()) {
+    memset(out, 0, 64);
+    out[0] = 0x40;
+  } else {
+    be32(out, from_mont(d.x).v);
+    be32(out + 32, from_mont(d.y).v);
+  }
+}
+Fr hash_to_fr_dst(const uint8_t* msg, size_t len, const char* dst) { return hash_to_fr(msg, len, dst); }
+
 void commit_keys_free(zkmi_ctx* ctx, zkmi_pk* pk) {
   for (auto& ck : pk->commits) {
     zkmi_msm_bases_free(ctx, ck.basis);
@@ -271,14 +283,7 @@ int commit_phase(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S, uint32_t index, bool writ
   std::vector<uint8_t> msg(64 + 32 * (size_t)ck.n_hashed);
   std::vector<Fr> vals(batch);
   for (size_t p = 0; p < batch; p++) {
-    const G1Affine& d = hpts[p];
-    if (d.x.is_zero() && d.y.is_zero()) {   // G1Affine.Marshal() of the point at infinity
-      memset(msg.data(), 0, 64);
-      msg[0] = 0x40;
-    } else {
-      be32(msg.data(), from_mont(d.x).v);
-      be32(msg.data() + 32, from_mont(d.y).v);
-    }
+    g1_marshal(msg.data(), hpts[p]);
     for (uint32_t j = 0; j < ck.n_hashed; j++)
       be32(msg.data() + 64 + 32 * j, domain_to_plain(row_get(hrows[j], p, Bp), S.f_domain).v);
     const Fr c = hash_to_fr(msg.data(), msg.size(), "bsb22-commitment");

@@ -17,6 +17,7 @@
 
 #include "zkmi_internal.h"
 #include "scs_check.h"
+#include "plonk_commit_check.h"
 #include "sha256.h"
 #include <atomic>
 #include <cstring>
@@ -45,6 +46,25 @@ struct zkmi_plonk_pk {
   DevBuf cf[4];      // coefficient forms of a, b, c, z: (n + 8) rows
   DevBuf big[6];     // 4n-row work buffers
   DevBuf small[4];   // challenges / per-proof scalars, MSM outputs
+  // ---- commitments (api.Commit under PLONK, zkmi_plonk_pk_set_commitments; empty for a plain key)
+  struct Commit {
+    uint32_t n_rows = 0, row = 0;
+    std::vector<uint32_t> slots;        // host: value-file slots of the operands (may be empty)
+    uint32_t* rows_dev = nullptr;       // n_rows + 2: C_i, then the blinding rows r_i and n - 1
+    uint32_t* slots_dev = nullptr;      // n_rows, or null
+    zkmi_msm_bases* lag = nullptr;      // subset-sum tables of the n_rows + 2 Lagrange points
+    size_t scal_row = 0;                // first row of this commitment's scalars in cm_scal
+  };
+  std::vector<Commit> commits;
+  Fr *qcp_coef = nullptr, *qcp_coset = nullptr;   // n_c x n (256 image), n_c x 4n (261 image)
+  uint8_t* cm_skip = nullptr;   // n bytes: 1 on committed and commitment rows (satisfied by construction)
+  bool proved = false;          // a prove has started on this key
+  DevBuf cm_scal;    // per commitment n_rows + 2 rows: the scalars of [pi2_i] (gnark's image)
+  DevBuf cm_blind;   // 2 n_c rows: the caller's blinding scalars
+  DevBuf cm_h;       // n_c rows: H_i
+  DevBuf cm_pi2;     // n_c x n rows: coefficient forms of pi2_i, from round 3 to round 5
+  std::vector<G1Affine> cm_pts;   // host: [pi2_i] of the batch in flight, proof-major (batch x n_c)
+  std::vector<Fr> cm_H;           // host: H_i, proof-major, Montgomery
 };
 
 namespace zk {
@@ -258,10 +278,14 @@ __global__ __launch_bounds__(64) void plonk_eval_combine(EvalArgs args, const Fr
 
 // numerators of the two openings.  sc rows: 0 qm, 1 ql, 2 qr, 3 qo, 4 s3, 5 z, 6 tlo, 7 tmid, 8 thi,
 // 9 c0 (constant term: r0 - sum_i v^i e_i), 10 v, 11 zeta, 12 zeta*w, 13 z(zeta w)
+// CM (key with n_c commitments): sc rows 14 + i = Qcp_i(zeta); the numerator at zeta gains
+// Qcp_i(zeta) pi2_i(X) (pi2: n_c x n rows, per proof) + v^(6+i) Qcp_i(X) (qcp: n_c x n, key side)
+template <bool CM>
 __global__ __launch_bounds__(64, 2) void plonk_lin(const Fr* ca, const Fr* cb, const Fr* cc,
                                                 const Fr* cz, const Fr* t, const Fr* kc,
                                                 const Fr* sc, Fr* N, Fr* NZ, size_t n, size_t Bp,
-                                                Fr c266) {
+                                                Fr c266, uint32_t n_c, const Fr* pi2,
+                                                const Fr* qcp) {
   // every product is (per-proof scalar) x (coefficient at 256): the scalars are lifted to 261 once
   // per lane (fmulp by 2^266: 256 + 266 - 261), the products then land at 256 (see fmulp)
   LANE;
@@ -281,6 +305,14 @@ __global__ __launch_bounds__(64, 2) void plonk_lin(const Fr* ca, const Fr* cb, c
               add(fmulp(sqo, kc[2 * n + i]), fmulp(sqm, kc[3 * n + i])));
       r = add(r, add(kc[4 * n + i], fmulp(ss3, kc[7 * n + i])));
       r = add(r, add(fmulp(v4F, kc[5 * n + i]), fmulp(v5F, kc[6 * n + i])));
+      if (CM) {   // scalars lifted to 261 as above, coefficients at 256
+        Fr vp = v5;
+        for (uint32_t k = 0; k < n_c; k++) {
+          vp = fmulp(vF, vp);   // v^(6+k): 261 + 256 - 261
+          r = add(r, add(fmulp(fmulp(bi_ld(sc, 14 + k, lane, Bp), c266), bi_ld(pi2, k * n + i, lane, Bp)),
+                         fmulp(fmulp(vp, c266), qcp[k * n + i])));
+        }
+      }
     }
     const Fr zi = bi_ld(cz, i, lane, Bp);
     r = add(r, fmulp(sz, zi));
@@ -372,11 +404,16 @@ __global__ __launch_bounds__(256) void plonk_l1_kernel(const Fr* xs, Fr* l1, siz
 // in gnark's image: qL qR qO qM are 2^261 images (fmulp: 256 + 261 - 261), a b = fmulp(a, 2^5 b)
 // likewise; a selector marked 0 / +1 / -1 (scs_check.h) takes no product.  Rows below n_public also
 // leave their a in `pub`, the public inputs round 3 and the transcript read.
+// For a key with commitments (CM), committed rows and commitment rows are satisfied by construction,
+// as the public rows are: their term of the gate equation, Qcp_i pi2_i resp. + H_i, is made from the
+// columns afterwards (plonk_commit_check compares H_i).  The mark is the key's: bit 0 of skip[g]
+// (the system's mark words are shared between keys).
 struct ScsDev {
   const uint32_t* x[3];
   const uint32_t* marks;
   const Fr* sel;
   uint32_t n_gates, n_public;
+  const uint8_t* skip;
 };
 __device__ __forceinline__ Fr scs_term(uint32_t mark, const Fr& x, const Fr* q) {
   if (mark == SCS_MARK_ZERO) return Fr::zero();
@@ -384,6 +421,7 @@ __device__ __forceinline__ Fr scs_term(uint32_t mark, const Fr& x, const Fr* q) 
   if (mark == SCS_MARK_MINUS_ONE) return neg(x);
   return fmulp(x, *q);
 }
+template <bool CM>
 __global__ __launch_bounds__(256) void scs_gate_kernel(ScsDev s, const Fr* __restrict__ w,
                                                        Fr* __restrict__ a, Fr* __restrict__ b,
                                                        Fr* __restrict__ c, Fr* __restrict__ pub,
@@ -407,8 +445,51 @@ __global__ __launch_bounds__(256) void scs_gate_kernel(ScsDev s, const Fr* __res
       sum = sub(sum, va);
       bi_st(pub, g, p, Bp, va);
     }
+    if (CM && s.skip[g]) continue;
     if (!sum.is_zero()) st[p] = ZKMI_ERR_UNSATISFIED;
   }
+}
+
+// ---- commitments (api.Commit) -------------------------------------------------------------------------
+// dst row j = src row idx[j]: the committed values of one commitment, out of the value file or out of
+// column a, as the rows of the matrix its MSM reads
+__global__ void plonk_commit_gather(const Fr* __restrict__ src, const uint32_t* __restrict__ idx,
+                                    Fr* __restrict__ dst, uint32_t count, size_t Bp) {
+  LANE;
+  for (uint32_t j = blockIdx.y; j < count; j += gridDim.y)
+    bi_st(dst, j, lane, Bp, bi_ld(src, idx[j], lane, Bp));
+}
+// col row idx[j] = src row j, j in [j0, j1): pi2_i as a column of the domain (every other row was zeroed)
+__global__ void plonk_commit_scatter(const Fr* __restrict__ src, const uint32_t* __restrict__ idx,
+                                     Fr* __restrict__ col, uint32_t j0, uint32_t j1, size_t Bp) {
+  LANE;
+  for (uint32_t j = j0 + blockIdx.y; j < j1; j += gridDim.y)
+    bi_st(col, idx[j], lane, Bp, bi_ld(src, j, lane, Bp));
+}
+// the solved columns against the commitments: a[r_i] must be H_i (one row of `h` per commitment)
+struct CommitRows {
+  uint32_t row[PLONK_MAX_COMMITMENTS];
+};
+__global__ void plonk_commit_check(const Fr* __restrict__ a, const Fr* __restrict__ h, CommitRows rows,
+                                   uint32_t n_c, int32_t* __restrict__ st, size_t Bp) {
+  LANE;
+  for (uint32_t i = 0; i < n_c; i++)
+    if (!(bi_ld(a, rows.row[i], lane, Bp) == bi_ld(h, i, lane, Bp))) st[lane] = ZKMI_ERR_UNSATISFIED;
+}
+// PI' beyond the public rows: + H_i at row r_i of the PI Lagrange column
+__global__ void plonk_pi_commit(Fr* __restrict__ pi, const Fr* __restrict__ h, CommitRows rows,
+                                uint32_t n_c, size_t Bp) {
+  LANE;
+  for (uint32_t i = 0; i < n_c; i++)
+    bi_st(pi, rows.row[i], lane, Bp, add(bi_ld(pi, rows.row[i], lane, Bp), bi_ld(h, i, lane, Bp)));
+}
+// epi += Qcp_i pi2_i on the coset.  Exponents (fmulp): pi2 256 (per-proof data), the wave-uniform
+// Qcp_i coset values 261 as stored by zkmi_plonk_pk_set_commitments: 256 + 261 - 261 = 256, as epi
+__global__ __launch_bounds__(64) void plonk_qcp_fold(const Fr* __restrict__ e, const Fr* __restrict__ q,
+                                                     Fr* __restrict__ epi, size_t m, size_t Bp) {
+  LANE;
+  for (size_t j = blockIdx.y; j < m; j += gridDim.y)
+    bi_st(epi, j, lane, Bp, add(bi_ld(epi, j, lane, Bp), fmulp(bi_ld(e, j, lane, Bp), q[j])));
 }
 
 static int buf(zkmi_ctx* ctx, DevBuf& b, size_t bytes) {
@@ -454,6 +535,115 @@ static int commit(zkmi_ctx* ctx, zkmi_plonk_pk* pk, int count, const Fr* const* 
   return ZKMI_OK;
 }
 
+// staging buffer of one round call: freed on every exit path, after the stream has drained
+struct RoundTmp {
+  zkmi_ctx* ctx;
+  void* p = nullptr;
+  explicit RoundTmp(zkmi_ctx* c) : ctx(c) {}
+  int alloc(size_t bytes) {
+    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      ctx->err = "plonk: hipMalloc(" + std::to_string(bytes) + " B) failed";
+      return ZKMI_ERR_OOM;
+    }
+    return ZKMI_OK;
+  }
+  ~RoundTmp() {
+    if (p) {
+      hipStreamSynchronize(ctx->stream);
+      hipFree(p);
+    }
+  }
+};
+
+// ---- the commitment step (shared by the solver path, the witness path and the hint entry) ----------
+// rows of commitment i's scalars in cm_scal; the buffers of a batch of Bp lanes
+static int commit_buffers(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t Bp) {
+  size_t rows = 0;
+  for (auto& c : pk->commits) {
+    c.scal_row = rows;
+    rows += c.n_rows + 2;
+  }
+  const size_t n_c = pk->commits.size();
+  int rc;
+  if ((rc = buf(ctx, pk->cm_scal, rows * Bp * 32)) || (rc = buf(ctx, pk->cm_blind, 2 * n_c * Bp * 32)) ||
+      (rc = buf(ctx, pk->cm_h, n_c * Bp * 32)) || (rc = buf(ctx, pk->small[2], Bp * 128)) ||
+      (rc = buf(ctx, pk->small[3], Bp * 64)))
+    return rc;
+  return ZKMI_OK;
+}
+static CommitRows commit_rows_of(const zkmi_plonk_pk* pk) {
+  CommitRows r{};
+  for (size_t i = 0; i < pk->commits.size(); i++) r.row[i] = pk->commits[i].row;
+  return r;
+}
+// With the n_rows committed values of commitment i in its rows of cm_scal (gnark's image) and its two
+// blinding scalars in `blind2` (two device rows): [pi2_i] = MSM over the n_rows + 2 Lagrange points
+// -> affine -> host; H_i = hash_to_field(marshal, "BSB22-Plonk") on the host -> row i of cm_h.
+// pts / hs: the host results of proof p at pts[p * stride], hs[p * stride].
+static int commit_step(zkmi_ctx* ctx, zkmi_plonk_pk* pk, uint32_t i, const Fr* blind2, size_t Bp,
+                       size_t batch, G1Affine* pts, Fr* hs, size_t stride) {
+  const zkmi_plonk_pk::Commit& c = pk->commits[i];
+  const size_t n = (size_t)1 << pk->log_n;
+  Fr* scal = (Fr*)pk->cm_scal.p + c.scal_row * Bp;
+  ZK_HIP(hipMemcpyAsync(scal + (size_t)c.n_rows * Bp, blind2, 2 * Bp * sizeof(Fr),
+                        hipMemcpyDeviceToDevice, ctx->stream));
+  if (c.row == n - 1)   // both blinding rows coincide: the second write wins
+    ZK_HIP(hipMemsetAsync(scal + (size_t)c.n_rows * Bp, 0, Bp * sizeof(Fr), ctx->stream));
+  int rc;
+  if ((rc = msm_run(ctx, c.lag, scal, nullptr, Bp, batch, pk->small[2].p)) ||
+      (rc = xyzz_to_affine(ctx, 1, pk->small[2].p, pk->small[3].p, Bp)))
+    return rc;
+  std::vector<G1Affine> hp(batch);
+  ZK_HIP(hipMemcpyAsync(hp.data(), pk->small[3].p, batch * 64, hipMemcpyDeviceToHost, ctx->stream));
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  std::vector<uint4> row(2 * Bp, make_uint4(0, 0, 0, 0));
+  uint8_t msg[64];
+  for (size_t p = 0; p < batch; p++) {
+    g1_marshal(msg, hp[p]);
+    const Fr h = hash_to_fr_dst(msg, 64, "BSB22-Plonk");
+    pts[p * stride] = hp[p];
+    hs[p * stride] = h;
+    row[p] = make_uint4(h.v[0], h.v[1], h.v[2], h.v[3]);
+    row[Bp + p] = make_uint4(h.v[4], h.v[5], h.v[6], h.v[7]);
+  }
+  ZK_HIP(hipMemcpyAsync((Fr*)pk->cm_h.p + (size_t)i * Bp, row.data(), 2 * Bp * 16, hipMemcpyHostToDevice,
+                        ctx->stream));
+  ZK_HIP(hipStreamSynchronize(ctx->stream));   // `row` is a local
+  return ZKMI_OK;
+}
+static inline unsigned grid_rows(size_t rows) { return (unsigned)std::min<size_t>(std::max<size_t>(rows, 1), 4096); }
+// the blinding scalars of the commitments: batch x 2 n_c fr -> rows of cm_blind; host result buffers
+static int commit_begin(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* blind_commit, size_t batch,
+                        size_t Bp) {
+  const size_t n_c = pk->commits.size();
+  int rc;
+  if ((rc = commit_buffers(ctx, pk, Bp))) return rc;
+  RoundTmp t(ctx);
+  if ((rc = t.alloc(batch * 2 * n_c * 32))) return rc;
+  ZK_HIP(hipMemcpyAsync(t.p, blind_commit, batch * 2 * n_c * 32, hipMemcpyDefault, ctx->stream));
+  if ((rc = transpose_in(ctx, t.p, pk->cm_blind.p, 2 * n_c, batch, Bp, 32))) return rc;
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  pk->cm_pts.assign(batch * n_c, G1Affine{});
+  pk->cm_H.assign(batch * n_c, Fr::zero());
+  return ZKMI_OK;
+}
+// commitment i from rows idx[0 .. n_rows) of `src` (column a, or the value file in the F domain)
+static int commit_from_rows(zkmi_ctx* ctx, zkmi_plonk_pk* pk, uint32_t i, const Fr* src,
+                            const uint32_t* idx, bool f_domain, size_t Bp, size_t batch) {
+  const zkmi_plonk_pk::Commit& c = pk->commits[i];
+  const size_t n_c = pk->commits.size();
+  Fr* scal = (Fr*)pk->cm_scal.p + c.scal_row * Bp;
+  hipLaunchKernelGGL(plonk_commit_gather, dim3((unsigned)(Bp / 64), grid_rows(c.n_rows)), dim3(64), 0,
+                     ctx->stream, src, idx, scal, c.n_rows, Bp);
+  ZK_HIP(hipGetLastError());
+  int rc;
+  if (f_domain && (rc = rows_to_std_domain(ctx, scal, c.n_rows, Bp))) return rc;
+  return commit_step(ctx, pk, i, (const Fr*)pk->cm_blind.p + (size_t)2 * i * Bp, Bp, batch,
+                     pk->cm_pts.data() + i, pk->cm_H.data() + i, n_c);
+}
+
 }  // namespace zk
 
 extern "C" {
@@ -478,6 +668,14 @@ void zkmi_plonk_pk_free(zkmi_ctx* ctx, zkmi_plonk_pk* pk) {
     if (b.p) hipFree(b.p);
   for (auto& b : pk->small)
     if (b.p) hipFree(b.p);
+  for (auto& c : pk->commits) {
+    zkmi_msm_bases_free(ctx, c.lag);
+    if (c.rows_dev) hipFree(c.rows_dev);
+    if (c.slots_dev) hipFree(c.slots_dev);
+  }
+  for (void* p : {(void*)pk->qcp_coef, (void*)pk->qcp_coset, (void*)pk->cm_skip, pk->cm_scal.p,
+                  pk->cm_blind.p, pk->cm_h.p, pk->cm_pi2.p})
+    if (p) hipFree(p);
   delete pk;
 }
 
@@ -597,28 +795,6 @@ int zkmi_plonk_pk_load(zkmi_ctx* ctx, const zkmi_plonk_pk_desc* d, zkmi_plonk_pk
   return ZKMI_OK;
 }
 
-// staging buffer of one round call: freed on every exit path, after the stream has drained
-struct RoundTmp {
-  zkmi_ctx* ctx;
-  void* p = nullptr;
-  explicit RoundTmp(zkmi_ctx* c) : ctx(c) {}
-  int alloc(size_t bytes) {
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      ctx->err = "plonk: hipMalloc(" + std::to_string(bytes) + " B) failed";
-      return ZKMI_ERR_OOM;
-    }
-    return ZKMI_OK;
-  }
-  ~RoundTmp() {
-    if (p) {
-      hipStreamSynchronize(ctx->stream);
-      hipFree(p);
-    }
-  }
-};
-
 // Round 1 is shared by its two entries (zkmi_plonk_round1: the solver; zkmi_plonk_round1_witness:
 // solved wires) apart from how the columns come to be.  round1_begin: the batch's buffers;
 // round1_tail, with the Lagrange values of a, b, c in rows [0, nc) of big[1..3]: inverse transforms,
@@ -629,14 +805,21 @@ static int round1_begin(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch) {
   pk->batch = batch;
   pk->Bp = Bp;
   pk->round = 0;
+  pk->proved = true;
   for (auto& b : pk->cf)
     if ((rc = buf(ctx, b, (n + 8) * Bp * 32))) return rc;
   for (auto& b : pk->big)
     if ((rc = buf(ctx, b, m * Bp * 32))) return rc;
-  if ((rc = buf(ctx, pk->small[0], 16 * Bp * 32)) || (rc = buf(ctx, pk->small[1], 16 * Bp * 32)))
+  // small[0]: the 9 blinding rows, then the evaluations, then the 14 (+ n_c) scalars of round 5
+  const size_t rows0 = pk->commits.empty() ? 16 : 24;
+  if ((rc = buf(ctx, pk->small[0], rows0 * Bp * 32)) || (rc = buf(ctx, pk->small[1], 16 * Bp * 32)))
     return rc;
+  if (!pk->commits.empty() && (rc = buf(ctx, pk->cm_pi2, pk->commits.size() * n * Bp * 32))) return rc;
   return ZKMI_OK;
 }
+static const char* const kNoCommitments =
+    "plonk: this key carries commitments: prove it with zkmi_plonk_prove_ex / "
+    "zkmi_plonk_prove_witness_ex (the plain and the round-by-round entries do not carry them)";
 static int round1_tail(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t nc, void* commits_out) {
   const size_t n = (size_t)1 << pk->log_n, Bp = pk->Bp, batch = pk->batch;
   Fr *A = (Fr*)pk->big[1].p, *B = (Fr*)pk->big[2].p, *C = (Fr*)pk->big[3].p;
@@ -684,8 +867,21 @@ static int round1_tail(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t nc, void* commit
 
 // Round 1: witness solve (the constraint system's rows are the gate columns a, b, c), blinding,
 // commitments [a], [b], [c].
+static int round1_solve(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
+                        size_t batch, const void* blind, const void* blind_commit, void* commits_out,
+                        int32_t* status_out);
 int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
                       size_t batch, const void* blind, void* commits_out, int32_t* status_out) {
+  if (!pk->commits.empty()) {
+    ctx->err = kNoCommitments;
+    return ZKMI_ERR_ARG;
+  }
+  return round1_solve(ctx, pk, cs, inputs, batch, blind, nullptr, commits_out, status_out);
+}
+// blind_commit: the blinding scalars of the key's commitments (null for a key without)
+static int round1_solve(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
+                        size_t batch, const void* blind, const void* blind_commit, void* commits_out,
+                        int32_t* status_out) {
   ZK_HIP(hipSetDevice(ctx->device));
   int rc;
   if ((rc = require_idle(ctx))) return rc;
@@ -698,7 +894,25 @@ int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const
     ctx->err = "plonk: constraint system does not match the key";
     return ZKMI_ERR_ARG;
   }
+  // the program's COMMIT rows are the key's commitments, in order, and every operand slot is a wire
+  const size_t n_c = pk->commits.size();
+  if (cs->commit_rows.size() != n_c) {
+    ctx->err = "plonk: the constraint system has " + std::to_string(cs->commit_rows.size()) +
+               " COMMIT rows, the key " + std::to_string(n_c) + " commitments";
+    return ZKMI_ERR_ARG;
+  }
+  for (size_t i = 0; i < n_c; i++) {
+    const auto& c = pk->commits[i];
+    bool ok = !c.slots.empty();
+    for (uint32_t sl : c.slots) ok = ok && sl < cs->n_wires;
+    if (!ok) {
+      ctx->err = "plonk: commitment " + std::to_string(i) +
+                 " has no operand slots, or one that is not a wire of the constraint system";
+      return ZKMI_ERR_ARG;
+    }
+  }
   if ((rc = round1_begin(ctx, pk, batch))) return rc;
+  if (n_c && (rc = commit_begin(ctx, pk, blind_commit, batch, Bp))) return rc;
   const size_t n_in = cs->n_public - 1 + cs->n_secret, nc = cs->n_constraints;
   // stage inputs + blinding scalars (host or device, proof-major)
   // value file and gate columns: big[0] = slots (reused later), big[1..3] = a, b, c; every size is
@@ -721,7 +935,25 @@ int zkmi_plonk_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const
   if (!rc) rc = transpose_in(ctx, in_dev, pk->big[5].p, n_in, batch, Bp, 32);
   if (!rc) rc = rows_to_f_domain(ctx, slots + Bp, n_in, Bp);
   if (!rc) rc = transpose_in(ctx, bl_dev, pk->small[0].p, 9, batch, Bp, 32);
-  if (!rc) rc = solve_bi(ctx, cs, slots, A, B, C, (int32_t*)st, Bp);
+  if (!rc && n_c == 0) {
+    rc = solve_bi(ctx, cs, slots, A, B, C, (int32_t*)st, Bp);
+  } else if (!rc) {
+    // the program stops at every COMMIT row: the commitment step on the operands' slots of the value
+    // file (F domain), H_i into the challenge wire's slot, and on
+    rc = solve_init(ctx, slots, (int32_t*)st, Bp);
+    uint32_t begin = 0;
+    for (size_t i = 0; !rc && i < n_c; i++) {
+      rc = solve_rows(ctx, cs, slots, A, B, C, (int32_t*)st, Bp, begin, cs->commit_rows[i].first);
+      if (!rc) rc = commit_from_rows(ctx, pk, (uint32_t)i, slots, pk->commits[i].slots_dev, true, Bp, batch);
+      Fr* wire = slots + (size_t)cs->commit_rows[i].second * Bp;
+      if (!rc && hipMemcpyAsync(wire, (const Fr*)pk->cm_h.p + i * Bp, Bp * sizeof(Fr),
+                                hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        rc = ZKMI_ERR_HIP;
+      if (!rc) rc = rows_to_f_domain(ctx, wire, 1, Bp);
+      begin = cs->commit_rows[i].first + 1;
+    }
+    if (!rc) rc = solve_rows(ctx, cs, slots, A, B, C, (int32_t*)st, Bp, begin, cs->n_rows);
+  }
   if (!rc) rc = rows_to_std_domain(ctx, A, nc, Bp);
   if (!rc) rc = rows_to_std_domain(ctx, B, nc, Bp);
   if (!rc) rc = rows_to_std_domain(ctx, C, nc, Bp);
@@ -801,7 +1033,9 @@ int zkmi_plonk_round3(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* alpha, void*
   // PI(X): Lagrange values (-x_j) from the public-input rows saved in big[5] -> coefficients
   // (big[0]) -> coset evaluations (big[5])
   // (circuits with more than eight public inputs; otherwise plonk_quotient evaluates PI itself)
-  const int n_pub_direct = pk->n_public <= 8 ? (int)pk->n_public : -1;
+  // (a key with commitments always takes the buffer: it then holds PI' + sum_i Qcp_i pi2_i)
+  const size_t n_c = pk->commits.size();
+  const int n_pub_direct = pk->n_public <= 8 && n_c == 0 ? (int)pk->n_public : -1;
   Fr *EA = (Fr*)pk->big[1].p, *EB = (Fr*)pk->big[2].p, *EC = (Fr*)pk->big[3].p,
      *EZ = (Fr*)pk->big[4].p, *EPI = (Fr*)pk->big[5].p;
   if (n_pub_direct < 0) {
@@ -809,11 +1043,39 @@ int zkmi_plonk_round3(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* alpha, void*
     hipLaunchKernelGGL(plonk_pi, dim3((unsigned)(Bp / 64), (unsigned)(n < 4096 ? n : 4096)),
                        dim3(64), 0, ctx->stream, (const Fr*)pk->big[5].p, pil, (size_t)pk->n_public, n,
                        Bp);
+    if (n_c)
+      hipLaunchKernelGGL(plonk_pi_commit, dim3((unsigned)(Bp / 64)), dim3(64), 0, ctx->stream, pil,
+                         (const Fr*)pk->cm_h.p, commit_rows_of(pk), (uint32_t)n_c, Bp);
     ZK_HIP(hipGetLastError());
     Fr* pic = pil + n * Bp;
     if ((rc = ntt_bi(ctx, plan_n, pil, pic, Bp, true, false, n)) ||
         (rc = ntt_bi(ctx, plan_m, pic, EPI, Bp, false, true, n)))
       return rc;
+  }
+  // Commitments.  PI' also holds + H_i at row r_i (added to the Lagrange column above, before its
+  // transforms: see the launch order below).  Then per commitment: pi2_i as a column of the domain
+  // (big[0] rows [0, n): zeroed, its n_rows + 2 scalars scattered; the blinding row n - 1 last, so
+  // that it wins where both blinding rows coincide) -> coefficient form, kept in cm_pi2 for round 5
+  // -> coset evaluations in big[4], which is free here (Z's Lagrange values are no longer needed and
+  // its coset evaluations are made below) -> epi += Qcp_i pi2_i.  No further 4n buffer.
+  for (size_t i = 0; i < n_c; i++) {
+    const zkmi_plonk_pk::Commit& c = pk->commits[i];
+    Fr* col = (Fr*)pk->big[0].p;
+    Fr* cf = (Fr*)pk->cm_pi2.p + i * n * Bp;
+    Fr* E = (Fr*)pk->big[4].p;
+    const Fr* scal = (const Fr*)pk->cm_scal.p + c.scal_row * Bp;
+    ZK_HIP(hipMemsetAsync(col, 0, n * Bp * sizeof(Fr), ctx->stream));
+    hipLaunchKernelGGL(plonk_commit_scatter, dim3((unsigned)(Bp / 64), grid_rows(c.n_rows + 1)), dim3(64),
+                       0, ctx->stream, scal, (const uint32_t*)c.rows_dev, col, 0u, c.n_rows + 1, Bp);
+    hipLaunchKernelGGL(plonk_commit_scatter, dim3((unsigned)(Bp / 64), 1), dim3(64), 0, ctx->stream, scal,
+                       (const uint32_t*)c.rows_dev, col, c.n_rows + 1, c.n_rows + 2, Bp);
+    ZK_HIP(hipGetLastError());
+    if ((rc = ntt_bi(ctx, plan_n, col, cf, Bp, true, false, n)) ||
+        (rc = ntt_bi(ctx, plan_m, cf, E, Bp, false, true, n)))
+      return rc;
+    hipLaunchKernelGGL(plonk_qcp_fold, dim3((unsigned)(Bp / 64), (unsigned)(m < 8192 ? m : 8192)), dim3(64),
+                       0, ctx->stream, (const Fr*)E, (const Fr*)(pk->qcp_coset + i * m), EPI, m, Bp);
+    ZK_HIP(hipGetLastError());
   }
   if ((rc = ntt_bi(ctx, plan_m, (Fr*)pk->cf[0].p, EA, Bp, false, true, n + 2)) ||
       (rc = ntt_bi(ctx, plan_m, (Fr*)pk->cf[1].p, EB, Bp, false, true, n + 2)) ||
@@ -837,7 +1099,14 @@ int zkmi_plonk_round3(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* alpha, void*
 }
 
 // Round 4: zeta (batch fr) -> a(zeta), b(zeta), c(zeta), S1(zeta), S2(zeta), z(zeta w)
+static int round4_run(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* zeta_zetaw, void* evals_out,
+                      void* qcp_out);
 int zkmi_plonk_round4(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* zeta_zetaw, void* evals_out) {
+  return round4_run(ctx, pk, zeta_zetaw, evals_out, nullptr);
+}
+// qcp_out (keys with commitments): batch x n_c fr, Qcp_i(zeta)
+static int round4_run(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* zeta_zetaw, void* evals_out,
+                      void* qcp_out) {
   ZK_HIP(hipSetDevice(ctx->device));
   if (pk->round != 3) {
     ctx->err = "plonk: round 4 out of order";
@@ -871,6 +1140,38 @@ int zkmi_plonk_round4(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* zeta_zetaw, 
   hipLaunchKernelGGL(plonk_eval_combine, dim3((unsigned)(Bp / 64), 6), dim3(64), 0, ctx->stream, ea,
                      (const Fr*)pts, (const Fr*)part, ev, n_chunks, Bp);
   ZK_HIP(hipGetLastError());
+  // Qcp_i(zeta): the same two kernels over the key-side coefficient forms, six slots per launch,
+  // into rows 6 .. 6 + n_c - 1 of ev; their chunk values behind the first launch's
+  const size_t n_c = pk->commits.size();
+  RoundTmp t4q(ctx);
+  if (n_c) {
+    if (!qcp_out) {
+      ctx->err = kNoCommitments;
+      return ZKMI_ERR_ARG;
+    }
+    if ((rc = t4q.alloc(batch * n_c * 32))) return rc;
+    for (size_t i0 = 0; i0 < n_c; i0 += 6) {
+      const unsigned cnt = (unsigned)std::min<size_t>(6, n_c - i0);
+      EvalArgs eq{};
+      for (unsigned k = 0; k < cnt; k++) {
+        eq.poly[k] = pk->qcp_coef + (i0 + k) * n;
+        eq.len[k] = (uint32_t)n;
+        eq.shared[k] = 1;
+        eq.point_row[k] = 0;
+      }
+      Fr* part_q = part + (size_t)(6 + i0) * n_chunks * Bp;
+      hipLaunchKernelGGL(plonk_chunk_horner, dim3((unsigned)(Bp / 64), n_chunks, cnt), dim3(64), 0,
+                         ctx->stream, eq, (const Fr*)pts, part_q, n_chunks, Bp);
+      hipLaunchKernelGGL(plonk_eval_combine, dim3((unsigned)(Bp / 64), cnt), dim3(64), 0, ctx->stream, eq,
+                         (const Fr*)pts, (const Fr*)part_q, ev + (6 + i0) * Bp, n_chunks, Bp);
+    }
+    ZK_HIP(hipGetLastError());
+    rc = transpose_out(ctx, ev + 6 * Bp, t4q.p, n_c, batch, Bp, 32);
+    if (!rc && hipMemcpyAsync(qcp_out, t4q.p, batch * n_c * 32, hipMemcpyDefault, ctx->stream) !=
+                   hipSuccess)
+      rc = ZKMI_ERR_HIP;
+    if (rc) return rc;
+  }
   void* out_dev = t4o.p;
   rc = transpose_out(ctx, ev, out_dev, 6, batch, Bp, 32);
   if (!rc && hipMemcpyAsync(evals_out, out_dev, batch * 6 * 32, hipMemcpyDefault, ctx->stream) !=
@@ -884,7 +1185,18 @@ int zkmi_plonk_round4(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* zeta_zetaw, 
 
 // Round 5: per-proof scalars of the linearisation polynomial and of the openings (batch x 14 fr,
 // see plonk_lin) -> commitments [W_zeta], [W_zeta_w]
+static int round5_run(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* scalars, size_t n_sc,
+                      void* commits_w_out);
 int zkmi_plonk_round5(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* scalars, void* commits_w_out) {
+  if (!pk->commits.empty()) {
+    ctx->err = kNoCommitments;
+    return ZKMI_ERR_ARG;
+  }
+  return round5_run(ctx, pk, scalars, 14, commits_w_out);
+}
+// n_sc = 14 + n_c scalars per proof: the 14 above, then Qcp_i(zeta)
+static int round5_run(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* scalars, size_t n_sc,
+                      void* commits_w_out) {
   ZK_HIP(hipSetDevice(ctx->device));
   if (pk->round != 4) {
     ctx->err = "plonk: round 5 out of order";
@@ -893,11 +1205,11 @@ int zkmi_plonk_round5(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* scalars, voi
   const size_t n = (size_t)1 << pk->log_n, Bp = pk->Bp, batch = pk->batch;
   int rc;
   RoundTmp t5(ctx);
-  if ((rc = t5.alloc(batch * 14 * 32))) return rc;
+  if ((rc = t5.alloc(batch * n_sc * 32))) return rc;
   void* tmp = t5.p;
-  ZK_HIP(hipMemcpyAsync(tmp, scalars, batch * 14 * 32, hipMemcpyDefault, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(tmp, scalars, batch * n_sc * 32, hipMemcpyDefault, ctx->stream));
   Fr* sc = (Fr*)pk->small[0].p;
-  rc = transpose_in(ctx, tmp, sc, 14, batch, Bp, 32);
+  rc = transpose_in(ctx, tmp, sc, n_sc, batch, Bp, 32);
   if (rc) return rc;
   const size_t L = n + 3;
   // numerators in big[2], quotients in big[3]: 2 (n + 8) rows each (log_n >= 4)
@@ -905,10 +1217,12 @@ int zkmi_plonk_round5(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const void* scalars, voi
   Fr* NZ = N + (n + 8) * Bp;
   Fr* W = (Fr*)pk->big[3].p;
   Fr* WZ = W + (n + 8) * Bp;
-  hipLaunchKernelGGL(plonk_lin, dim3((unsigned)(Bp / 64), (unsigned)(L < 4096 ? L : 4096)),
+  const auto lin = pk->commits.empty() ? plonk_lin<false> : plonk_lin<true>;
+  hipLaunchKernelGGL(lin, dim3((unsigned)(Bp / 64), (unsigned)(L < 4096 ? L : 4096)),
                      dim3(64), 0, ctx->stream, (const Fr*)pk->cf[0].p, (const Fr*)pk->cf[1].p,
                      (const Fr*)pk->cf[2].p, (const Fr*)pk->cf[3].p, (const Fr*)pk->big[1].p,
-                     (const Fr*)pk->coef, (const Fr*)sc, N, NZ, n, Bp, pow2_image(266));
+                     (const Fr*)pk->coef, (const Fr*)sc, N, NZ, n, Bp, pow2_image(266),
+                     (uint32_t)pk->commits.size(), (const Fr*)pk->cm_pi2.p, (const Fr*)pk->qcp_coef);
   hipLaunchKernelGGL(plonk_zero_rows, dim3((unsigned)(Bp / 64), 8), dim3(64), 0, ctx->stream, W, L - 1,
                      n + 8, Bp);
   hipLaunchKernelGGL(plonk_zero_rows, dim3((unsigned)(Bp / 64), 8), dim3(64), 0, ctx->stream, WZ,
@@ -1021,12 +1335,17 @@ extern "C" {
 
 // Rounds 2 .. 5 with the transcript between them, after either round 1: pubs = batch x n_public public
 // inputs (gnark's image, host), abc = the commitments of round 1; assembles the records
+// For a key with n_c commitments (pk->cm_pts, pk->cm_H: what round 1 left): [pi2_i] enter alpha, the
+// Qcp_i(zeta) enter v after the six evaluations, PI(zeta) gains H_i L_(r_i)(zeta), the scalars of
+// round 5 gain the Qcp_i(zeta), and commit_out takes batch x n_c x 96 bytes.
 static int prove_after_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch, const std::vector<Fr>& pubs,
                               const std::vector<G1Affine>& abc, const uint8_t* vk_digest,
-                              void* proofs_out) {
-  const size_t n = (size_t)1 << pk->log_n, n_pub = pk->n_public;
+                              void* proofs_out, void* commit_out = nullptr) {
+  const size_t n = (size_t)1 << pk->log_n, n_pub = pk->n_public, n_c = pk->commits.size();
+  const size_t n_sc = 14 + n_c;
   std::vector<G1Affine> cz(batch), ct(batch * 3), cw(batch * 2);
-  std::vector<Fr> bg(batch * 2), al(batch), zz(batch * 2), ev(batch * 6), sc(batch * 14);
+  std::vector<Fr> bg(batch * 2), al(batch), zz(batch * 2), ev(batch * 6), sc(batch * n_sc),
+      eq(batch * n_c);
   int rc;
   for (size_t p = 0; p < batch; p++) {
     Transcript t("gamma");
@@ -1043,6 +1362,7 @@ static int prove_after_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch, co
   for (size_t p = 0; p < batch; p++) {
     Transcript t("alpha");
     t.fr_mont(bg[2 * p]);
+    for (size_t i = 0; i < n_c; i++) t.point(pk->cm_pts[p * n_c + i]);
     t.point(cz[p]);
     al[p] = t.challenge();
   }
@@ -1057,7 +1377,7 @@ static int prove_after_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch, co
     zz[2 * p] = t.challenge();
     zz[2 * p + 1] = mul(zz[2 * p], w);
   }
-  if ((rc = zkmi_plonk_round4(ctx, pk, zz.data(), ev.data()))) return rc;
+  if ((rc = round4_run(ctx, pk, zz.data(), ev.data(), n_c ? eq.data() : nullptr))) return rc;
   const Fr ninv = inverse(fr_u64(n)), five = fr_u64(5), tf = fr_u64(25);
   // 1 / (zeta - w^j), j = 0 .. max(n_pub, 1) - 1 (j = 0 also serves L_1), for every proof: one
   // inversion in all (Montgomery's trick); zeta = w^j has probability 2^-250
@@ -1088,6 +1408,7 @@ static int prove_after_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch, co
     Transcript t("v");
     t.fr_mont(zeta);
     for (int k = 0; k < 6; k++) t.fr_mont(e[k]);
+    for (size_t i = 0; i < n_c; i++) t.fr_mont(eq[p * n_c + i]);
     const Fr v = t.challenge();
     // scalars of the linearisation polynomial (plonk.py::lin_scalars)
     const Fr zh = sub(fr_pow_u64(zeta, n), Fr::one());
@@ -1098,12 +1419,17 @@ static int prove_after_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch, co
       pi = sub(pi, mul(pubs[p * n_pub + j], lj));
       wj = mul(wj, w);
     }
+    for (size_t i = 0; i < n_c; i++) {   // + H_i L_(r_i)(zeta)
+      const Fr wr = fr_pow_u64(w, pk->commits[i].row);
+      const Fr lr = mul(mul(mul(zh, wr), ninv), inverse(sub(zeta, wr)));
+      pi = add(pi, mul(pk->cm_H[p * n_c + i], lr));
+    }
     const Fr bz = mul(beta, zeta);
     const Fr a1 = mul(mul(add(add(e[0], bz), gamma), add(add(e[1], mul(five, bz)), gamma)),
                       add(add(e[2], mul(tf, bz)), gamma));
     const Fr a2 = mul(add(add(e[0], mul(beta, e[3])), gamma), add(add(e[1], mul(beta, e[4])), gamma));
     const Fr zn2 = fr_pow_u64(zeta, n + 2), al2 = mul(alpha, alpha);
-    Fr* s = sc.data() + 14 * p;
+    Fr* s = sc.data() + n_sc * p;
     s[0] = mul(e[0], e[1]);                                        // qm
     s[1] = e[0];                                                   // ql
     s[2] = e[1];                                                   // qr
@@ -1119,13 +1445,18 @@ static int prove_after_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch, co
       vp = mul(vp, v);
       c0 = sub(c0, mul(vp, e[k]));
     }
+    for (size_t i = 0; i < n_c; i++) {   // v^(6+i) Qcp_i(zeta)
+      vp = mul(vp, v);
+      c0 = sub(c0, mul(vp, eq[p * n_c + i]));
+      s[14 + i] = eq[p * n_c + i];
+    }
     s[9] = c0;
     s[10] = v;
     s[11] = zeta;
     s[12] = zz[2 * p + 1];
     s[13] = e[5];
   }
-  if ((rc = zkmi_plonk_round5(ctx, pk, sc.data(), cw.data()))) return rc;
+  if ((rc = round5_run(ctx, pk, sc.data(), n_sc, cw.data()))) return rc;
   // assemble the records on the host, one copy out (host or device destination)
   std::vector<uint8_t> rec(batch * 768);
   for (size_t p = 0; p < batch; p++) {
@@ -1137,16 +1468,47 @@ static int prove_after_round1(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch, co
     memcpy(r + 576, &ev[p * 6], 192);
   }
   ZK_HIP(hipMemcpy(proofs_out, rec.data(), rec.size(), hipMemcpyDefault));
+  if (n_c) {
+    std::vector<uint8_t> cm(batch * n_c * 96);
+    for (size_t k = 0; k < batch * n_c; k++) {
+      memcpy(cm.data() + k * 96, &pk->cm_pts[k], 64);
+      memcpy(cm.data() + k * 96 + 64, &eq[k], 32);
+    }
+    ZK_HIP(hipMemcpy(commit_out, cm.data(), cm.size(), hipMemcpyDefault));
+  }
   return ZKMI_OK;
 }
 
 /* proofs_out: batch x 96 words of 8 bytes = 9 G1 affine points ([a] [b] [c] [z] [t_lo] [t_mid] [t_hi]
  * [W_zeta] [W_zeta_w], Montgomery) then 6 fr (a, b, c, S1, S2 at zeta, z at zeta w; Montgomery). */
+// the extras of a key with commitments are both given, those of a key without both null
+static int commit_args_check(zkmi_ctx* ctx, const zkmi_plonk_pk* pk, const void* blind_commit,
+                             const void* commit_out) {
+  const bool has = !pk->commits.empty();
+  if (has ? (!blind_commit || !commit_out) : (blind_commit || commit_out)) {
+    ctx->err = has ? "plonk: a key with commitments needs blind_commit and commit_out"
+                   : "plonk: blind_commit / commit_out given for a key without commitments";
+    return ZKMI_ERR_ARG;
+  }
+  return ZKMI_OK;
+}
 int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
                      size_t batch, const void* blind, const uint8_t* vk_digest /* 32 bytes */,
                      void* proofs_out, int32_t* status_out) {
+  if (ctx && pk && !pk->commits.empty()) {
+    ctx->err = kNoCommitments;
+    return ZKMI_ERR_ARG;
+  }
+  return zkmi_plonk_prove_ex(ctx, pk, cs, inputs, batch, blind, nullptr, vk_digest, proofs_out, nullptr,
+                             status_out);
+}
+int zkmi_plonk_prove_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
+                        size_t batch, const void* blind, const void* blind_commit,
+                        const uint8_t* vk_digest, void* proofs_out, void* commit_out,
+                        int32_t* status_out) {
   if (!ctx || !pk || !cs || !inputs || !blind || !vk_digest || !proofs_out || !status_out || batch == 0)
     return ZKMI_ERR_ARG;
+  if (int bad = commit_args_check(ctx, pk, blind_commit, commit_out)) return bad;
   const size_t n_pub = pk->n_public;
   const size_t n_in = cs->n_public - 1 + cs->n_secret;
   // public inputs on the host (gnark's image)
@@ -1158,9 +1520,9 @@ int zkmi_plonk_prove(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const 
       return ZKMI_ERR_HIP;
     }
   std::vector<G1Affine> abc(batch * 3);
-  int rc = zkmi_plonk_round1(ctx, pk, cs, inputs, batch, blind, abc.data(), status_out);
+  int rc = round1_solve(ctx, pk, cs, inputs, batch, blind, blind_commit, abc.data(), status_out);
   if (rc) return rc;
-  return prove_after_round1(ctx, pk, batch, pubs, abc, vk_digest, proofs_out);
+  return prove_after_round1(ctx, pk, batch, pubs, abc, vk_digest, proofs_out, commit_out);
 }
 
 // ---- the gnark drop-in entry: key from the trace form, round 1 from solved witnesses ----------------
@@ -1331,10 +1693,25 @@ int zkmi_scs_load(zkmi_ctx* ctx, const zkmi_scs_desc* d, zkmi_scs** out) {
   return ZKMI_OK;
 }
 
+static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs, const void* wires,
+                          const void* a, const void* b, const void* c, size_t n_gates, size_t batch,
+                          const void* blind, const void* blind_commit, void* commits_out,
+                          int32_t* status_out);
 int zkmi_plonk_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
                               const void* wires, const void* a, const void* b, const void* c,
                               size_t n_gates, size_t batch, const void* blind, void* commits_out,
                               int32_t* status_out) {
+  if (pk && !pk->commits.empty()) {
+    ctx->err = kNoCommitments;
+    return ZKMI_ERR_ARG;
+  }
+  return round1_witness(ctx, pk, scs, wires, a, b, c, n_gates, batch, blind, nullptr, commits_out,
+                        status_out);
+}
+static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs, const void* wires,
+                          const void* a, const void* b, const void* c, size_t n_gates, size_t batch,
+                          const void* blind, const void* blind_commit, void* commits_out,
+                          int32_t* status_out) {
   ZK_HIP(hipSetDevice(ctx->device));
   int rc;
   if ((rc = require_idle(ctx))) return rc;
@@ -1386,8 +1763,10 @@ int zkmi_plonk_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* 
     }
     scs->checked_key = pk->serial;
   }
+  const size_t n_c = pk->commits.size();
   if ((rc = round1_begin(ctx, pk, batch))) return rc;
   const size_t Bp = pk->Bp;
+  if (n_c && (rc = commit_begin(ctx, pk, blind_commit, batch, Bp))) return rc;
   RoundTmp tbl(ctx);
   if ((rc = tbl.alloc(batch * 9 * 32))) return rc;
   ZK_HIP(hipMemcpyAsync(tbl.p, blind, batch * 9 * 32, hipMemcpyDefault, ctx->stream));
@@ -1401,8 +1780,8 @@ int zkmi_plonk_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* 
     rc = stage_rows(ctx, wires, scs->n_wires, batch, Bp, W);
     if (!rc) {
       const ScsDev dev{{scs->x[0], scs->x[1], scs->x[2]}, scs->marks, scs->sel, scs->n_gates,
-                       scs->n_public};
-      hipLaunchKernelGGL(scs_gate_kernel,
+                       scs->n_public, pk->cm_skip};
+      hipLaunchKernelGGL(n_c ? scs_gate_kernel<true> : scs_gate_kernel<false>,
                          dim3((unsigned)(Bp / 64), (unsigned)std::min<size_t>((n_gates + 3) / 4, 32768)),
                          dim3(256), 0, ctx->stream, dev, (const Fr*)W, A, B, C, pub, (int32_t*)st, Bp);
       if (hipGetLastError() != hipSuccess) rc = ZKMI_ERR_HIP;
@@ -1414,6 +1793,21 @@ int zkmi_plonk_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* 
     if (!rc && n_pub &&
         hipMemcpyAsync(pub, A, n_pub * Bp * 32, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
       rc = ZKMI_ERR_HIP;
+  }
+  // commitments: the step for every i from column a (rows >= n_gates of the domain read as zero, as
+  // round 2 reads them), then a[r_i] against H_i
+  if (!rc && n_c) {
+    if (n_gates < n)
+      hipLaunchKernelGGL(plonk_zero_rows, dim3((unsigned)(Bp / 64), 64), dim3(64), 0, ctx->stream, A,
+                         n_gates, n, Bp);
+    for (size_t i = 0; !rc && i < n_c; i++)
+      rc = commit_from_rows(ctx, pk, (uint32_t)i, A, pk->commits[i].rows_dev, false, Bp, batch);
+    if (!rc) {
+      hipLaunchKernelGGL(plonk_commit_check, dim3((unsigned)(Bp / 64)), dim3(64), 0, ctx->stream,
+                         (const Fr*)A, (const Fr*)pk->cm_h.p, commit_rows_of(pk), (uint32_t)n_c,
+                         (int32_t*)st, Bp);
+      if (hipGetLastError() != hipSuccess) rc = ZKMI_ERR_HIP;
+    }
   }
   // the caller's arrays have been consumed once the stream has passed the copies
   if (hipStreamSynchronize(ctx->stream) != hipSuccess && !rc) rc = ZKMI_ERR_HIP;
@@ -1429,14 +1823,27 @@ int zkmi_plonk_prove_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* s
                              const void* wires, const void* a, const void* b, const void* c,
                              size_t n_gates, size_t batch, const void* blind,
                              const uint8_t* vk_digest, void* proofs_out, int32_t* status_out) {
+  if (ctx && pk && !pk->commits.empty()) {
+    ctx->err = kNoCommitments;
+    return ZKMI_ERR_ARG;
+  }
+  return zkmi_plonk_prove_witness_ex(ctx, pk, scs, wires, a, b, c, n_gates, batch, blind, nullptr,
+                                     vk_digest, proofs_out, nullptr, status_out);
+}
+int zkmi_plonk_prove_witness_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
+                                const void* wires, const void* a, const void* b, const void* c,
+                                size_t n_gates, size_t batch, const void* blind,
+                                const void* blind_commit, const uint8_t* vk_digest, void* proofs_out,
+                                void* commit_out, int32_t* status_out) {
   if (!ctx) return ZKMI_ERR_ARG;
   if (!pk || !blind || !vk_digest || !proofs_out || !status_out || batch == 0) {
     ctx->err = "plonk_prove_witness: null argument or empty batch";
     return ZKMI_ERR_ARG;
   }
+  if (int bad = commit_args_check(ctx, pk, blind_commit, commit_out)) return bad;
   std::vector<G1Affine> abc(batch * 3);
-  int rc = zkmi_plonk_round1_witness(ctx, pk, scs, wires, a, b, c, n_gates, batch, blind, abc.data(),
-                                     status_out);
+  int rc = round1_witness(ctx, pk, scs, wires, a, b, c, n_gates, batch, blind, blind_commit, abc.data(),
+                          status_out);
   if (rc) return rc;
   // public inputs: column a of rows 0 .. n_public - 1, which round 1 left in big[5]
   const size_t n_pub = pk->n_public;
@@ -1449,7 +1856,164 @@ int zkmi_plonk_prove_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* s
     ZK_HIP(hipMemcpyAsync(pubs.data(), t.p, batch * n_pub * 32, hipMemcpyDeviceToHost, ctx->stream));
     ZK_HIP(hipStreamSynchronize(ctx->stream));
   }
-  return prove_after_round1(ctx, pk, batch, pubs, abc, vk_digest, proofs_out);
+  return prove_after_round1(ctx, pk, batch, pubs, abc, vk_digest, proofs_out, commit_out);
+}
+
+// ---- commitments of a key (api.Commit under PLONK; parity with gnark unpinned) ----------------------
+// Qcp_i: indicator column of C_i -> coefficient form -> coset evaluations in the 2^261 image the other
+// selectors have, by the prover's own transforms, the commitments being the lanes of one batch-inner
+// matrix of 64 (as pk_from_trace computes the eight key polynomials).
+int zkmi_plonk_pk_set_commitments(zkmi_ctx* ctx, zkmi_plonk_pk* pk,
+                                  const zkmi_plonk_commit_desc* descs, uint32_t n_c) {
+  if (!ctx) return ZKMI_ERR_ARG;
+  if (!pk) {
+    ctx->err = "plonk commitments: no key";
+    return ZKMI_ERR_ARG;
+  }
+  ZK_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
+  const size_t n = (size_t)1 << pk->log_n, m = 4 * n, Bp = 64;
+  // host copies of the rows, then every check before anything is built
+  const uint32_t cnt = descs ? std::min<uint32_t>(n_c, PLONK_MAX_COMMITMENTS + 1) : 0;
+  std::vector<std::vector<uint32_t>> rows(cnt);
+  std::vector<PlonkCommitShape> shapes(cnt);
+  for (uint32_t i = 0; i < cnt; i++) {
+    const zkmi_plonk_commit_desc& d = descs[i];
+    if (d.rows && d.n_rows && d.n_rows <= n) {
+      rows[i].resize(d.n_rows);
+      ZK_HIP(hipMemcpy(rows[i].data(), d.rows, (size_t)d.n_rows * 4, hipMemcpyDefault));
+    }
+    shapes[i] = PlonkCommitShape{d.n_rows, rows[i].empty() ? nullptr : rows[i].data(), d.row,
+                                 d.lag_g1 != nullptr, d.lag_k};
+    if (d.n_rows > n) shapes[i].rows = &d.row;   // refused by its count before a row is read
+  }
+  const std::string bad = plonk_commit_validate(
+      shapes.data(), n_c > PLONK_MAX_COMMITMENTS ? n_c : cnt,
+      PlonkCommitKeyState{n, !pk->commits.empty(), pk->proved});
+  if (!bad.empty()) {
+    ctx->err = bad;
+    return ZKMI_ERR_ARG;
+  }
+  // built aside; the key takes them only when all of it has succeeded
+  std::vector<zkmi_plonk_pk::Commit> cm(n_c);
+  Fr *qcoef = nullptr, *qcoset = nullptr;
+  uint8_t* skip = nullptr;
+  auto undo = [&](int code) {
+    hipStreamSynchronize(ctx->stream);
+    for (auto& c : cm) {
+      zkmi_msm_bases_free(ctx, c.lag);
+      if (c.rows_dev) hipFree(c.rows_dev);
+      if (c.slots_dev) hipFree(c.slots_dev);
+    }
+    for (void* p : {(void*)qcoef, (void*)qcoset, (void*)skip})
+      if (p) hipFree(p);
+    (void)hipGetLastError();
+    if (code == ZKMI_ERR_HIP && ctx->err.empty()) ctx->err = "plonk commitments: HIP error while building";
+    return code;
+  };
+  std::vector<Fr> ind((size_t)n_c * n, Fr::zero());
+  std::vector<uint8_t> hskip(n, 0);
+  for (uint32_t i = 0; i < n_c; i++) {
+    const zkmi_plonk_commit_desc& d = descs[i];
+    zkmi_plonk_pk::Commit& c = cm[i];
+    c.n_rows = d.n_rows;
+    c.row = d.row;
+    std::vector<uint32_t> all(rows[i]);
+    all.push_back(d.row);
+    all.push_back((uint32_t)(n - 1));
+    for (uint32_t r : rows[i]) {
+      ind[(size_t)i * n + r] = Fr::one();
+      hskip[r] = 1;
+    }
+    hskip[d.row] = 1;
+    bool ok = hipMalloc((void**)&c.rows_dev, all.size() * 4) == hipSuccess &&
+              hipMemcpy(c.rows_dev, all.data(), all.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && d.slots) {
+      c.slots.resize(d.n_rows);
+      ok = hipMemcpy(c.slots.data(), d.slots, (size_t)d.n_rows * 4, hipMemcpyDefault) == hipSuccess &&
+           hipMalloc((void**)&c.slots_dev, (size_t)d.n_rows * 4) == hipSuccess &&
+           hipMemcpy(c.slots_dev, c.slots.data(), (size_t)d.n_rows * 4, hipMemcpyHostToDevice) ==
+               hipSuccess;
+    }
+    if (!ok) return undo(ZKMI_ERR_HIP);
+    // 200 + k: subset-sum comb tables (zero digits are skipped: the scalars are mostly nibbles and bytes)
+    const uint32_t k = d.lag_k ? d.lag_k : plonk_commit_auto_k(d.n_rows + 2);
+    if ((rc = zkmi_msm_bases_load(ctx, 1, d.lag_g1, (size_t)d.n_rows + 2, 200 + (int)k, &c.lag)))
+      return undo(rc);
+  }
+  NttPlan *plan_n, *plan_m;
+  if ((rc = get_plan(ctx, (int)pk->log_n, &plan_n)) || (rc = get_plan(ctx, (int)pk->log_n + 2, &plan_m)))
+    return undo(rc);
+  {
+    RoundTmp lag(ctx), mat_n(ctx), mat_m(ctx);
+    if ((rc = lag.alloc((size_t)n_c * n * 32)) || (rc = mat_n.alloc(n * Bp * 32)) ||
+        (rc = mat_m.alloc(m * Bp * 32)))
+      return undo(rc);
+    if (hipMalloc((void**)&qcoef, (size_t)n_c * n * 32) != hipSuccess ||
+        hipMalloc((void**)&qcoset, (size_t)n_c * m * 32) != hipSuccess ||
+        hipMalloc((void**)&skip, n) != hipSuccess ||
+        hipMemcpy(skip, hskip.data(), n, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(lag.p, ind.data(), (size_t)n_c * n * 32, hipMemcpyHostToDevice) != hipSuccess)
+      return undo(ZKMI_ERR_HIP);
+    Fr *Mn = (Fr*)mat_n.p, *Mm = (Fr*)mat_m.p;
+    // lanes n_c .. 63 of the matrices carry nothing that is read back
+    if (hipMemsetAsync(Mm, 0, n * Bp * 32, ctx->stream) != hipSuccess) return undo(ZKMI_ERR_HIP);
+    if ((rc = transpose_in(ctx, lag.p, Mm, n, n_c, Bp, 32)) ||
+        (rc = ntt_bi(ctx, plan_n, Mm, Mn, Bp, true, false, n)) ||
+        (rc = transpose_out(ctx, Mn, qcoef, n, n_c, Bp, 32)) ||
+        (rc = ntt_bi(ctx, plan_m, Mn, Mm, Bp, false, true, n)) ||
+        (rc = transpose_out(ctx, Mm, qcoset, m, n_c, Bp, 32)))
+      return undo(rc);
+    hipLaunchKernelGGL(plonk_lift_kernel, dim3((unsigned)(((size_t)n_c * m + 255) / 256)), dim3(256), 0,
+                       ctx->stream, qcoset, (size_t)n_c * m, 5);   // 2^261 image (plonk_qcp_fold)
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+      return undo(ZKMI_ERR_HIP);
+  }
+  pk->commits = std::move(cm);
+  pk->qcp_coef = qcoef;
+  pk->qcp_coset = qcoset;
+  pk->cm_skip = skip;
+  return ZKMI_OK;
+}
+
+int zkmi_plonk_commit_hint(zkmi_ctx* ctx, zkmi_plonk_pk* pk, uint32_t index, const void* values,
+                           const void* blind2, size_t batch, void* commit_out, void* h_out) {
+  if (!ctx) return ZKMI_ERR_ARG;
+  if (!pk || !values || !blind2 || !commit_out || !h_out) {
+    ctx->err = "plonk commit hint: null argument";
+    return ZKMI_ERR_ARG;
+  }
+  ZK_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
+  if (index >= pk->commits.size()) {
+    ctx->err = "plonk commit hint: the key has " + std::to_string(pk->commits.size()) +
+               " commitments, index " + std::to_string(index);
+    return ZKMI_ERR_ARG;
+  }
+  if (batch == 0 || batch > pk->max_batch) {
+    ctx->err = "plonk: batch must be in [1, max_batch]";
+    return ZKMI_ERR_ARG;
+  }
+  const size_t Bp = round_up(batch, 64);
+  if ((rc = commit_buffers(ctx, pk, Bp))) return rc;
+  const zkmi_plonk_pk::Commit& c = pk->commits[index];
+  RoundTmp tv(ctx), tb(ctx);
+  if ((rc = tv.alloc(batch * c.n_rows * 32)) || (rc = tb.alloc(batch * 64))) return rc;
+  ZK_HIP(hipMemcpyAsync(tv.p, values, batch * c.n_rows * 32, hipMemcpyDefault, ctx->stream));
+  ZK_HIP(hipMemcpyAsync(tb.p, blind2, batch * 64, hipMemcpyDefault, ctx->stream));
+  Fr* scal = (Fr*)pk->cm_scal.p + c.scal_row * Bp;
+  Fr* bl = (Fr*)pk->cm_blind.p + (size_t)2 * index * Bp;
+  if ((rc = transpose_in(ctx, tv.p, scal, c.n_rows, batch, Bp, 32)) ||
+      (rc = transpose_in(ctx, tb.p, bl, 2, batch, Bp, 32)))
+    return rc;
+  std::vector<G1Affine> pts(batch);
+  std::vector<Fr> hs(batch);
+  if ((rc = commit_step(ctx, pk, index, bl, Bp, batch, pts.data(), hs.data(), 1))) return rc;
+  ZK_HIP(hipMemcpy(commit_out, pts.data(), batch * 64, hipMemcpyDefault));
+  ZK_HIP(hipMemcpy(h_out, hs.data(), batch * 32, hipMemcpyDefault));
+  return ZKMI_OK;
 }
 
 }  // extern "C"

@@ -471,6 +471,10 @@ int commit_phase(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S, uint32_t index, bool writ
 int commit_finish_submit(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S);
 // proof of knowledge on ctx->stream (main stream, enqueue_heavy)
 int commit_pok(zkmi_ctx* ctx, zkmi_ctx::ProveSet& S);
+// host: G1Affine.Marshal() (64 bytes) and fr.Hash(msg, dst, 1)[0] in gnark's image, shared with the
+// PLONK commitments (plonk.hip)
+void g1_marshal(uint8_t out[64], const G1Affine& d);
+Fr hash_to_fr_dst(const uint8_t* msg, size_t len, const char* dst);
 int commit_keys_load(zkmi_ctx* ctx, const zkmi_pk_desc* d, zkmi_pk* pk);
 void commit_keys_free(zkmi_ctx* ctx, zkmi_pk* pk);
 int rows_to_f_domain(zkmi_ctx* ctx, Fr* base, size_t rows, size_t Bp);

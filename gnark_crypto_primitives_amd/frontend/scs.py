@@ -23,13 +23,26 @@ Hints (inverse-or-zero, bit decomposition, unchecked division, the batched inver
 as in the R1CS, the rows that use their outputs constrain them.  The witness program of the system
 is the same program with an OP_ABC row per gate, so the GPU solver (csrc/solve.hip) emits the
 three wire columns a, b, c directly.
+
+api.Commit (gnark's scs builder, BSB22 [UPSTREAM-RECALL]; parity unpinned) is carried by one more
+selector column per commitment, Qcp_i, and the gate equation becomes
+    qL a + qR b + qO c + qM a b + qC + PI' + sum_i Qcp_i pi2_i = 0,   PI'_(r_i) = +H_i.
+Every operand w of commitment i (private, public or an earlier commitment wire, in operand order)
+gets a committed row (w, w, w) with qL = -1 and Qcp_i = 1, so pi2_i = a there; the commitment wire
+h_i gets the commitment row r_i: (h_i, h_i, h_i) with qL = -1, where the prover's
+H_i = hash_to_field([pi2_i]) enters as a public-input term.  The OP_COMMIT unit stays in the witness
+program as it is for the R1CS (the solver stops there and the prover supplies the challenge); the
+lookup multiplicities (OP_HIST), the emulated products (OP_EMUL) and the byte hints lower as hints.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .api import (OP_ABC, OP_ADD, OP_ADDC, OP_BATCHINV, OP_BITS, OP_COPY, OP_DIV, OP_INV, OP_MUL,
-                  OP_MULABC, OP_MULC, OP_NEG, OP_PAIR, OP_SETC, OP_SUB, OP_XOR, OP_XORABC, R)
+import hashlib
+
+from .api import (OP_ABC, OP_ADD, OP_ADDC, OP_BAND, OP_BATCHINV, OP_BITS, OP_BXOR, OP_COMMIT, OP_COPY,
+                  OP_DIV, OP_EMUL, OP_HIST, OP_HQ, OP_INV, OP_MUL, OP_MULABC, OP_MULC, OP_NEG, OP_PAIR,
+                  OP_SETC, OP_SUB, OP_XOR, OP_XORABC, R)
 from .compile import CompiledCircuit, build_vprogram
 
 COSET_SHIFT = 5          # fr.MultiplicativeGen: the columns' identity permutation is X, 5X, 25X
@@ -54,6 +67,8 @@ class ScsCircuit:
             gates.append((j, j, j, 1, 0, 0, 0, 0))
         gates.append((one, one, one, 1, 0, 0, 0, R - 1))
         prog, row_of, chk = [], {}, {}
+        self.commitments = []                  # {"rows": committed rows, "row": r_i, "wire", "val"}
+        commit_vals = []                       # per commitment: SSA values of its operands
 
         def gate(g, check=0):
             row_of[len(prog)] = len(gates)
@@ -63,7 +78,32 @@ class ScsCircuit:
 
         C = self.consts
         k_row = 0
+        pending = None                         # the OP_COMMIT unit whose operand rows are being read
         for op, d, a, b in ops:
+            if pending is not None and op != OP_HQ:
+                raise AssertionError("OP_COMMIT unit cut short")
+            if op == OP_COMMIT:
+                pending = [d, a, b, []]
+                if a == 0:
+                    raise AssertionError("OP_COMMIT without operands")
+                continue
+            if op == OP_HQ and pending is not None:
+                pending[3].append(a)
+                if len(pending[3]) == pending[1]:
+                    h, _, idx, reads = pending
+                    pending = None
+                    if idx != len(self.commitments):
+                        raise AssertionError("commitments out of order")
+                    rows = []
+                    for v in reads:            # committed rows, operand order
+                        rows.append(len(gates))
+                        gate((v, v, v, R - 1, 0, 0, 0, 0))
+                    prog.append((OP_COMMIT, h, len(reads), idx))
+                    prog.extend((OP_HQ, 0, v, 0) for v in reads)
+                    self.commitments.append({"rows": rows, "row": len(gates), "val": h})
+                    commit_vals.append(list(reads))
+                    gate((h, h, h, R - 1, 0, 0, 0, 0))
+                continue
             if op == OP_ABC:
                 gate((d, a, b, 0, 0, R - 1, 1, 0), 1 if cc._row_check[k_row] else 0)
                 k_row += 1
@@ -100,7 +140,8 @@ class ScsCircuit:
             elif op == OP_SETC:
                 prog.append((op, d, a, b))
                 gate((d, d, d, 0, 0, R - 1, 0, C[b]))
-            elif op in (OP_INV, OP_DIV, OP_BITS, OP_BATCHINV, OP_PAIR):
+            elif op in (OP_INV, OP_DIV, OP_BITS, OP_BATCHINV, OP_PAIR, OP_HIST, OP_HQ, OP_EMUL,
+                        OP_BXOR, OP_BAND):
                 prog.append((op, d, a, b))     # hints: constrained by the rows that use them
             else:
                 raise AssertionError(op)
@@ -120,6 +161,29 @@ class ScsCircuit:
          self.schedule_cost) = build_vprogram(prog, val_wire, row_of, chk, cc.n_wires,
                                               lanes_per_proof)
         self._build_tables()
+        # commitments: the wire numbers a shim sees (wiring()), the operands' value slots for the CPU
+        # evaluation of the program, and the Qcp columns on the domain
+        xa = self.wiring()[0]
+        n = 1 << self.log_n
+        self.qcp = []
+        for c, vals in zip(self.commitments, commit_vals):
+            c["wire"] = int(xa[c["row"]])
+            c["slots"] = [val_wire[v] for v in vals]
+            col = np.zeros(n, dtype=object)
+            col[c["rows"]] = 1
+            self.qcp.append(col)
+        self.commit_fn = None      # run_vprogram: (index, committed values in operand order) -> int
+
+    def _commit_value(self, idx, s):
+        """challenge of commitment ``idx`` from the value file: ``commit_fn(idx, committed values)``
+        (plonk side: hash of [pi2_idx]); without one, a SHA-256 stand-in, as for the R1CS."""
+        vals = [s[w] for w in self.commitments[idx]["slots"]]
+        if self.commit_fn is not None:
+            return int(self.commit_fn(idx, vals)) % R
+        h = hashlib.sha256(b"stand-in plonk commitment %d" % idx)
+        for v in vals:
+            h.update(int(v).to_bytes(32, "big"))
+        return int.from_bytes(h.digest(), "big") % R
 
     # the CPU evaluation of the scheduled program is the R1CS one (same machinery)
     run_vprogram = CompiledCircuit.run_vprogram
@@ -206,12 +270,22 @@ class ScsCircuit:
                     w[xw] = vals[g]
         return out
 
-    def is_satisfied(self, a, b, c, public):
-        """gate equations + copy constraints on full columns (lists of ints, length n_gates)."""
+    def is_satisfied(self, a, b, c, public, pi2=None, H=None):
+        """gate equations + copy constraints on full columns (lists of ints, length n_gates).
+        pi2: per commitment, its Lagrange values (a sequence over the gate rows, or {row: value});
+        H: per commitment, the value hashed from [pi2_i].  Left out, they are what the columns
+        imply (pi2_i = a on the committed rows, H_i = a at the commitment row)."""
         g = self.gates
         n_pub = self.n_public - 1
+        extra = {}                             # row -> PI' + sum_i Qcp_i pi2_i beyond the public rows
+        for i, cm in enumerate(self.commitments):
+            r = cm["row"]
+            extra[r] = (extra.get(r, 0) + (a[r] if H is None else H[i])) % R
+            for row in cm["rows"]:
+                v = a[row] if pi2 is None else pi2[i][row]
+                extra[row] = (extra.get(row, 0) + v) % R
         for i, (wa, wb, wc, qL, qR, qO, qM, qC) in enumerate(g):
-            pi = (-public[i]) % R if i < n_pub else 0
+            pi = ((-public[i]) % R if i < n_pub else 0) + extra.get(i, 0)
             if (qL * a[i] + qR * b[i] + qO * c[i] + qM * a[i] * b[i] + qC + pi) % R:
                 return False, i
         n = 1 << self.log_n
@@ -227,8 +301,4 @@ def compile_scs(circuit, lanes_per_proof: int = 0) -> ScsCircuit:
     """``frontend.Compile(field, scs.NewBuilder, circuit)`` look-alike."""
     from .compile import compile_circuit
     cc = circuit if isinstance(circuit, CompiledCircuit) else compile_circuit(circuit)
-    if getattr(cc, "commitments", None):
-        # gnark's PLONK carries api.Commit through an extra selector column (Qcp) and commitments to
-        # the committed wires' Lagrange polynomials [UPSTREAM-RECALL]: not built for this lowering
-        raise NotImplementedError("circuits that call api.Commit are Groth16 / R1CS only here")
     return ScsCircuit(cc, lanes_per_proof)

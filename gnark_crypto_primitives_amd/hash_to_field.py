@@ -10,6 +10,7 @@ import hashlib
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 COMMITMENT_DST = b"bsb22-commitment"
 POK_DST = b"G16-BSB22"
+PLONK_DST = b"BSB22-Plonk"      # value of a commitment wire under PLONK: Hash([pi2_i].Marshal())
 
 
 def expand_message_xmd(msg: bytes, dst: bytes, length: int) -> bytes:

@@ -75,6 +75,12 @@ class ScsDesc(C.Structure):
                 ("selectors", C.c_void_p)]
 
 
+class PlonkCommitDesc(C.Structure):
+    _fields_ = [("n_rows", C.c_uint32), ("row", C.c_uint32), ("rows", C.c_void_p),
+                ("slots", C.c_void_p), ("lag_g1", C.c_void_p), ("lag_k", C.c_uint32)]
+
+
+PLONK_MAX_COMMITMENTS = 8                               # ZKMI_PLONK_MAX_COMMITMENTS
 HINTS_BASIC, HINTS_STD, HINTS_EMULATED = 0, 1, 3      # enum zkmi_hint_set (2 alone is not a set)
 
 
@@ -139,6 +145,11 @@ SYMBOLS = [
     ("zkmi_scs_free", None, [_P, _P]),
     ("zkmi_plonk_round1_witness", _I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _P]),
     ("zkmi_plonk_prove_witness", _I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P]),
+    ("zkmi_plonk_pk_set_commitments", _I, [_P, _P, C.POINTER(PlonkCommitDesc), C.c_uint32]),
+    ("zkmi_plonk_commit_hint", _I, [_P, _P, C.c_uint32, _P, _P, _SZ, _P, _P]),
+    ("zkmi_plonk_prove_ex", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
+    ("zkmi_plonk_prove_witness_ex", _I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P, _P,
+                                         _P]),
 ]
 
 _lib = None

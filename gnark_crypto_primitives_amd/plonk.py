@@ -15,6 +15,12 @@ Protocol: a, b, c blinded by (b1 X + b2) Z_H, z by (b7 X^2 +
 gamma = H("gamma", vk, public, [a], [b], [c]); beta = H("beta", gamma); alpha = H("alpha", beta,
 [z]); zeta = H("zeta", alpha, [t_lo], [t_mid], [t_hi]); v = H("v", zeta, evaluations); u = H("u", v,
 [W_zeta], [W_zeta_w]).  Quotient chunks hold n + 2 coefficients.
+
+Circuits that call api.Commit (gnark's BSB22 under PLONK [UPSTREAM-RECALL]; parity unpinned): the key
+carries one selector Qcp_i per commitment (frontend/scs.py), the proof [pi2_i] and Qcp_i(zeta);
+H_i = hash_to_field([pi2_i].Marshal(), "BSB22-Plonk") enters PI at the commitment row;
+alpha = H("alpha", beta, [pi2_0], .., [z]); v absorbs the Qcp_i(zeta) after the six evaluations.  Such
+keys prove through ``prove_raw`` only (zkmi_plonk_prove_ex / zkmi_plonk_prove_witness_ex).
 """
 from __future__ import annotations
 
@@ -25,6 +31,7 @@ import random
 
 import numpy as np
 
+from . import hash_to_field as _h2f
 from . import lib as _lib
 from . import verify as _verify
 from .frontend.compile import array_to_ints, ints_to_array, to_mont_array
@@ -89,6 +96,9 @@ class ProvingKey:
         self.com = {}              # name -> G1 point (ints) of qL..qC, S1..S3
         self.g2_tau = None
         self.vk_digest = b""
+        # api.Commit: per commitment {"rows", "row", "slots"} (frontend/scs.py) and [Qcp_i]
+        self.commitments = []
+        self.qcp_com = []
 
 
 _NAMES = ("ql", "qr", "qo", "qm", "qc", "s1", "s2", "s3")
@@ -165,17 +175,74 @@ def setup(ctx: _lib.Context, scs: ScsCircuit, seed: int) -> ProvingKey:
         l1[j] = zh[j % 4] * ninv % R * (inv * pref[j] % R) % R
         inv = inv * den[j] % R
     pk.l1 = to_mont_array(l1)
-    # commitments of the 8 key polynomials: one MSM with the polynomials as the batch
+    # api.Commit: the selectors Qcp_i (frontend/scs.py) in coefficient form, committed with the rest
+    pk.commitments = [{"rows": list(c["rows"]), "row": c["row"], "slots": list(c["slots"])}
+                      for c in getattr(scs, "commitments", [])]
+    n_c = len(pk.commitments)
+    polys = coef
+    if n_c:
+        qcoef = np.stack([to_mont_array([int(v) for v in col]) for col in scs.qcp])
+        ctx.ntt_batch(qcoef, log_n, n_c, inverse=True, coset=False)
+        polys = np.ascontiguousarray(np.concatenate([coef, qcoef]))
+    # commitments of the 8 (+ n_c) key polynomials: one MSM with the polynomials as the batch
     h = ctx.msm_bases_load(1, pk.srs_g1[:n], n, 0)
-    pts = np.zeros((8, 8), dtype=np.uint64)
-    ctx.msm_batch(h, coef, 8, pts)
+    pts = np.zeros((8 + n_c, 8), dtype=np.uint64)
+    ctx.msm_batch(h, polys, 8 + n_c, pts)
     ctx.msm_bases_free(h)
     pk.com = {name: _verify.g1_from_image(pts[i]) for i, name in enumerate(_NAMES)}
+    pk.qcp_com = [_verify.g1_from_image(pts[8 + i]) for i in range(n_c)]
     # [tau]_2 on the host (one scalar multiplication; the verifier's side)
     pk.g2_tau = _g2_mul(_G2_GEN, tau)
+    # the digest absorbs r_i and [Qcp_i] only when there are any: a key without commitments keeps its
+    # digest
+    extra = []
+    for c, pt in zip(pk.commitments, pk.qcp_com):
+        extra += [c["row"], pt]
     pk.vk_digest = challenge("vk", pk.log_n, pk.n_public,
-                             *[pk.com[k] for k in _NAMES]).to_bytes(32, "big")
+                             *[pk.com[k] for k in _NAMES], *extra).to_bytes(32, "big")
     return pk
+
+
+def commitment_hash(pt) -> int:
+    """H_i of a commitment [pi2_i] (ints or None)"""
+    return _h2f.hash_fr(_h2f.g1_marshal(pt), _h2f.PLONK_DST)[0]
+
+
+def seeded_commit_fn(scs: ScsCircuit, seed: int, blind_commit):
+    """``ScsCircuit.commit_fn`` for the seeded (test) SRS of ``setup(ctx, scs, seed)``: H_i of one
+    proof with the blinding scalars ``blind_commit`` (2 n_c integers), from tau itself -- [pi2_i] is
+    one scalar multiplication of the generator.  Host solver of tests and tools only."""
+    tau = random.Random(seed).randrange(2, R)
+    n, w = 1 << scs.log_n, root_of_unity(scs.log_n)
+    zn = (pow(tau, n, R) - 1) * _inv(n) % R
+    lag = lambda g: pow(w, g, R) * zn % R * _inv(tau - pow(w, g, R)) % R
+
+    def fn(i, vals):
+        c = scs.commitments[i]
+        s = sum(v * lag(g) for v, g in zip(vals, c["rows"]))
+        s += blind_commit[2 * i + 1] * lag(n - 1)
+        if c["row"] != n - 1:
+            s += blind_commit[2 * i] * lag(c["row"])
+        return commitment_hash(_verify._g1_mul((1, 2), s % R))
+    return fn
+
+
+def set_commitments(ctx, pk: ProvingKey, pk_h, keep, lag_k: int = 0):
+    """zkmi_plonk_pk_set_commitments for the key handle ``pk_h``: per commitment its rows, its
+    operands' value-file slots and the Lagrange points of its rows and of the two blinding rows."""
+    if not pk.commitments:
+        return
+    n = 1 << pk.log_n
+    descs = (_lib.PlonkCommitDesc * len(pk.commitments))()
+    for d, c in zip(descs, pk.commitments):
+        rows = np.array(c["rows"], dtype=np.uint32)
+        slots = np.array(c["slots"], dtype=np.uint32)
+        pts = np.ascontiguousarray(pk.srs_lagrange[list(c["rows"]) + [c["row"], n - 1]])
+        keep += [rows, slots, pts]
+        d.n_rows, d.row, d.rows, d.slots = len(rows), c["row"], rows.ctypes.data, slots.ctypes.data
+        d.lag_g1, d.lag_k = pts.ctypes.data, lag_k
+    ctx._check(ctx.lib.zkmi_plonk_pk_set_commitments(ctx.h, pk_h, descs, len(descs)),
+               "zkmi_plonk_pk_set_commitments")
 
 
 # ---- small G2 arithmetic for [tau]_2 (host, once per key) -------------------------------------------
@@ -215,9 +282,10 @@ def _g2_mul(p, k):
     return out
 
 
-def lin_scalars(pk, public, beta, gamma, alpha, zeta, ev):
+def lin_scalars(pk, public, beta, gamma, alpha, zeta, ev, H=()):
     """Per-proof scalars of the linearisation polynomial
-    r(X) = qm qM + ql qL + qr qR + qo qO + qC + s3 S3 + z z(X) + tlo t_lo + tmid t_mid + thi t_hi + r0."""
+    r(X) = qm qM + ql qL + qr qR + qo qO + qC + s3 S3 + z z(X) + tlo t_lo + tmid t_mid + thi t_hi + r0
+    (+ sum_i Qcp_i(zeta) pi2_i(X) for a key with commitments, whose H_i enter PI(zeta) in r0)."""
     n = 1 << pk.log_n
     ea, eb, ec, es1, es2, ezw = ev
     zh = (pow(zeta, n, R) - 1) % R
@@ -227,6 +295,9 @@ def lin_scalars(pk, public, beta, gamma, alpha, zeta, ev):
     for j, x in enumerate(public):
         wj = pow(w, j, R)
         pi = (pi - x * (zh * wj % R * _inv(n) % R * _inv(zeta - wj) % R)) % R
+    for c, h in zip(pk.commitments, H):
+        wr = pow(w, c["row"], R)
+        pi = (pi + h * (zh * wr % R * _inv(n) % R * _inv(zeta - wr) % R)) % R
     a1 = (ea + beta * zeta + gamma) * (eb + 5 * beta * zeta + gamma) % R * \
         (ec + 25 * beta * zeta + gamma) % R
     a2 = (ea + beta * es1 + gamma) * (eb + beta * es2 + gamma) % R
@@ -239,16 +310,20 @@ def lin_scalars(pk, public, beta, gamma, alpha, zeta, ev):
 
 
 class Proof:
-    """plonk.Proof: 9 commitments (G1, ints or None) + 6 evaluations."""
+    """plonk.Proof: 9 commitments (G1, ints or None) + 6 evaluations; for a key with commitments
+    also ``bsb`` = [pi2_i] and ``ev_qcp`` = Qcp_i(zeta)."""
     FIELDS = ("a", "b", "c", "z", "tlo", "tmid", "thi", "wz", "wzw")
 
     def __init__(self, **kw):
         for f in self.FIELDS:
             setattr(self, f, kw.get(f))
         self.ev = tuple(kw.get("ev", ()))
+        self.bsb = list(kw.get("bsb", ()))
+        self.ev_qcp = tuple(kw.get("ev_qcp", ()))
 
     def __eq__(self, other):
-        return all(getattr(self, f) == getattr(other, f) for f in self.FIELDS) and self.ev == other.ev
+        return all(getattr(self, f) == getattr(other, f) for f in self.FIELDS) and \
+            self.ev == other.ev and self.bsb == other.bsb and self.ev_qcp == other.ev_qcp
 
 
 class Prover:
@@ -290,6 +365,7 @@ class Prover:
         h = C.c_void_p()
         ctx._check(ctx.lib.zkmi_plonk_pk_load(ctx.h, C.byref(d), C.byref(h)), "zkmi_plonk_pk_load")
         self.pk_h = h
+        set_commitments(ctx, pk, h, self._keep)
 
     def close(self):
         if getattr(self, "pk_h", None):
@@ -299,11 +375,13 @@ class Prover:
             self.ctx.cs_free(self.cs_h)
             self.cs_h = None
 
-    def prove_raw(self, inputs, blind):
+    def prove_raw(self, inputs, blind, blind_commit=None):
         """plonk.Prove through zkmi_plonk_prove: the five rounds with the transcript hashed in C++
         inside the library (no Python between the rounds).  Returns (records uint64 [batch, 96]: nine
         G1 points then six evaluations, gnark's Montgomery image; status [batch]); ``proofs_of``
-        turns records into Proof values."""
+        turns records into Proof values.  A key with n_c commitments takes blind_commit
+        [batch, 2 n_c, 4] (zkmi_plonk_prove_ex) and returns (records, status, commit records uint64
+        [batch, n_c, 12]: [pi2_i] then Qcp_i(zeta))."""
         batch = inputs.shape[0]
         if tuple(inputs.shape) != (batch, self.scs.n_inputs, 4) or tuple(blind.shape) != (batch, 9, 4):
             raise ValueError("inputs must be [batch, n_inputs, 4], blind [batch, 9, 4]")
@@ -311,6 +389,15 @@ class Prover:
         rec = np.zeros((batch, 96), dtype=np.uint64)
         status = np.zeros(batch, dtype=np.int32)
         vkd = (C.c_uint8 * 32).from_buffer_copy(self.pk.vk_digest)
+        n_c = len(self.pk.commitments)
+        if n_c:
+            blind_commit = _blind_commit(blind_commit, batch, n_c)
+            cm = np.zeros((batch, n_c, 12), dtype=np.uint64)
+            self.ctx._check(self.ctx.lib.zkmi_plonk_prove_ex(
+                self.ctx.h, self.pk_h, self.cs_h, inputs.ctypes.data, batch, blind.ctypes.data,
+                blind_commit.ctypes.data, vkd, rec.ctypes.data, cm.ctypes.data, status.ctypes.data),
+                "zkmi_plonk_prove_ex")
+            return rec, status, cm
         self.ctx._check(self.ctx.lib.zkmi_plonk_prove(self.ctx.h, self.pk_h, self.cs_h,
                                                       inputs.ctypes.data, batch, blind.ctypes.data,
                                                       vkd, rec.ctypes.data, status.ctypes.data),
@@ -318,14 +405,21 @@ class Prover:
         return rec, status
 
     @staticmethod
-    def proofs_of(rec):
-        """records of prove_raw -> list of Proof"""
+    def proofs_of(rec, commit_rec=None):
+        """records of prove_raw (and its commit records, for a key with commitments) -> list of
+        Proof"""
         rinv = pow(1 << 256, R - 2, R)
         out = []
-        for r in np.ascontiguousarray(rec, dtype=np.uint64).reshape(-1, 96):
+        for i, r in enumerate(np.ascontiguousarray(rec, dtype=np.uint64).reshape(-1, 96)):
             pts = [_verify.g1_from_image(r[8 * k:8 * k + 8]) for k in range(9)]
             ev = tuple(v * rinv % R for v in array_to_ints(r[72:96].reshape(6, 4)))
-            out.append(Proof(**dict(zip(Proof.FIELDS, pts)), ev=ev))
+            extra = {}
+            if commit_rec is not None:
+                cm = np.ascontiguousarray(commit_rec[i], dtype=np.uint64)
+                extra = {"bsb": [_verify.g1_from_image(c[:8]) for c in cm],
+                         "ev_qcp": tuple(v * rinv % R for v in array_to_ints(
+                             np.ascontiguousarray(cm[:, 8:12])))}
+            out.append(Proof(**dict(zip(Proof.FIELDS, pts)), ev=ev, **extra))
         return out
 
     def prove(self, inputs, blind):
@@ -334,6 +428,9 @@ class Prover:
         Python: the reference implementation of the transcript that ``prove_raw`` (C++) is tested
         against."""
         ctx, pk = self.ctx, self.pk
+        if pk.commitments:
+            raise ValueError("a key with commitments proves through prove_raw only: the "
+                             "round-by-round calls do not carry them")
         batch = inputs.shape[0]
         if tuple(inputs.shape) != (batch, self.scs.n_inputs, 4) or tuple(blind.shape) != (batch, 9, 4):
             raise ValueError("inputs must be [batch, n_inputs, 4], blind [batch, 9, 4]")
@@ -346,6 +443,12 @@ class Prover:
                                                  batch, blind.ctypes.data, c_abc.ctypes.data,
                                                  status.ctypes.data), "zkmi_plonk_round1")
         return _prove_rounds(ctx, pk, self.pk_h, batch, pubs, round1)
+
+
+def _blind_commit(blind_commit, batch, n_c):
+    if blind_commit is None or tuple(blind_commit.shape) != (batch, 2 * n_c, 4):
+        raise ValueError("a key with commitments needs blind_commit [batch, 2 n_c, 4]")
+    return np.ascontiguousarray(blind_commit)
 
 
 def _prove_rounds(ctx, pk, pk_h, batch, pubs, round1):
@@ -440,6 +543,7 @@ class WitnessProver:
         self.pk_h = ctx.plonk_pk_load_trace(_lib.PlonkTraceDesc(
             pk.log_n, pk.n_public, sel.ctypes.data, perm.ctypes.data, srs.ctypes.data, window_bits,
             max_batch, lag_g1, lag_rows, lag_k))
+        set_commitments(ctx, pk, self.pk_h, self._keep)
         gsel = np.ascontiguousarray(sel[:, :self.n_gates])
         xs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (xa, xb, xc)]
         self.scs_h = ctx.scs_load(_lib.ScsDesc(self.n_wires, self.n_gates, pk.n_public,
@@ -479,16 +583,25 @@ class WitnessProver:
             raise ValueError("blind must be [batch, 9, 4]")
         return batch, wit, pubs
 
-    def prove_raw(self, blind, wires=None, columns=None):
+    def prove_raw(self, blind, wires=None, columns=None, blind_commit=None):
         """plonk.Prove through zkmi_plonk_prove_witness.  wires: [batch, n_wires, 4] (Montgomery; a
         numpy array, pageable or from Context.host_alloc, or a device tensor); or columns = (a, b,
         c), [batch, n_gates, 4] each, taken as they are.  Returns (records, status) as
-        Prover.prove_raw does."""
+        Prover.prove_raw does; for a key with commitments, with blind_commit, (records, status,
+        commit records) through zkmi_plonk_prove_witness_ex."""
         batch, wit, _ = self._args(blind, wires, columns)
         blind = np.ascontiguousarray(blind)
         rec = np.zeros((batch, 96), dtype=np.uint64)
         status = np.zeros(batch, dtype=np.int32)
         vkd = (C.c_uint8 * 32).from_buffer_copy(self.pk.vk_digest)
+        n_c = len(self.pk.commitments)
+        if n_c:
+            blind_commit = _blind_commit(blind_commit, batch, n_c)
+            cm = np.zeros((batch, n_c, 12), dtype=np.uint64)
+            self.ctx._check(self.ctx.lib.zkmi_plonk_prove_witness_ex(
+                self.ctx.h, self.pk_h, *wit, batch, blind.ctypes.data, blind_commit.ctypes.data, vkd,
+                rec.ctypes.data, cm.ctypes.data, status.ctypes.data), "zkmi_plonk_prove_witness_ex")
+            return rec, status, cm
         self.ctx._check(self.ctx.lib.zkmi_plonk_prove_witness(
             self.ctx.h, self.pk_h, *wit, batch, blind.ctypes.data, vkd, rec.ctypes.data,
             status.ctypes.data), "zkmi_plonk_prove_witness")
@@ -498,6 +611,9 @@ class WitnessProver:
         """The round-by-round twin of prove_raw: zkmi_plonk_round1_witness, then Prover.prove's
         rounds and Python transcript.  Returns (list of Proof, status)."""
         ctx = self.ctx
+        if self.pk.commitments:
+            raise ValueError("a key with commitments proves through prove_raw only: the "
+                             "round-by-round calls do not carry them")
         batch, wit, pubs = self._args(blind, wires, columns)
         blind = np.ascontiguousarray(blind)
         rinv = pow(1 << 256, R - 2, R)
@@ -517,20 +633,25 @@ def verify(pk: ProvingKey, public, proof: Proof) -> bool:
     com = pk.com
     # canonical encodings only: challenge() reduces mod r, so an unreduced public input or claimed
     # evaluation would alias a reduced one
-    if any(not (0 <= int(x) < R) for x in public) or any(not (0 <= int(e) < R) for e in proof.ev):
+    n_c = len(pk.commitments)
+    if any(not (0 <= int(x) < R) for x in public) or \
+            any(not (0 <= int(e) < R) for e in tuple(proof.ev) + tuple(proof.ev_qcp)):
+        return False
+    if len(proof.bsb) != n_c or len(proof.ev_qcp) != n_c:
         return False
     gamma = challenge("gamma", pk.vk_digest, *public, proof.a, proof.b, proof.c)
     beta = challenge("beta", gamma)
-    alpha = challenge("alpha", beta, proof.z)
+    alpha = challenge("alpha", beta, *proof.bsb, proof.z)
     zeta = challenge("zeta", alpha, proof.tlo, proof.tmid, proof.thi)
     ev = proof.ev
-    v = challenge("v", zeta, *ev)
+    v = challenge("v", zeta, *ev, *proof.ev_qcp)
+    H = [commitment_hash(pt) for pt in proof.bsb]
     # the folding challenge of the two openings is chained to the whole transcript through v (which
     # binds zeta, every evaluation and, through zeta / alpha / beta / gamma, all nine commitments and
     # the public inputs) -- as gnark derives its KZG folding randomness from digests, points and
     # claimed values; a u that depended on [W_zeta], [W_zeta_w] alone could be fixed in advance
     u = challenge("u", v, proof.wz, proof.wzw)
-    sc = lin_scalars(pk, public, beta, gamma, alpha, zeta, ev)
+    sc = lin_scalars(pk, public, beta, gamma, alpha, zeta, ev, H)
     w = root_of_unity(pk.log_n)
     add, mul, neg = _verify._g1_add, _verify._g1_mul, _verify._g1_neg
     sm = lambda pt, s: None if pt is None else mul(pt, s)
@@ -546,13 +667,17 @@ def verify(pk: ProvingKey, public, proof: Proof) -> bool:
         vp = vp * v % R
         F = add(F, sm(pt, vp))
         E = (E + vp * e) % R
+    for i in range(n_c):       # Qcp_i(zeta) [pi2_i] in the linearisation; v^(6+i) Qcp_i opened at zeta
+        vp = vp * v % R
+        F = add(F, add(sm(proof.bsb[i], proof.ev_qcp[i]), sm(pk.qcp_com[i], vp)))
+        E = (E + vp * proof.ev_qcp[i]) % R
     F = add(F, sm(proof.z, u))
     E = (E + u * ev[5]) % R
     lhs = add(proof.wz, sm(proof.wzw, u))
     rhs = add(add(sm(proof.wz, zeta), sm(proof.wzw, u * zeta % R * w % R)),
               add(F, neg(mul((1, 2), E))))
     for pt in (proof.a, proof.b, proof.c, proof.z, proof.tlo, proof.tmid, proof.thi, proof.wz,
-               proof.wzw):
+               proof.wzw, *proof.bsb):
         if not _verify._on_g1(pt):
             return False
     return _verify.pairing_product_is_one([(lhs, pk.g2_tau), (neg(rhs), _G2_GEN)])

@@ -609,6 +609,59 @@ int zkmi_plonk_prove_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* s
                              size_t n_gates, size_t batch, const void* blind,
                              const uint8_t* vk_digest, void* proofs_out, int32_t* status_out);
 
+/* -- PLONK: circuits that call api.Commit (BSB22; the Qcp selector columns) ------------------------- */
+/* What gnark's PLONK backend does for api.Commit [UPSTREAM-RECALL]; parity unpinned, as for the rest
+ * of the PLONK prover.  A key carries n_c <= ZKMI_PLONK_MAX_COMMITMENTS commitments.  Commitment i has
+ * its committed rows C_i (gate rows, public rows counted, ascending), where the selector Qcp_i is 1,
+ * and its commitment row r_i; the gate equation becomes
+ *   qL a + qR b + qO c + qM a b + qC + PI'_g + sum_i Qcp_i,g pi2_i,g = 0,   PI'_(r_i) = +H_i.
+ * pi2_i is the Lagrange-form polynomial that holds a_g on C_i, the caller's blinding scalars at row
+ * r_i and at the last row of the key's domain, 2^log_n - 1 (where both coincide, the second one), and
+ * zero elsewhere; [pi2_i] its KZG commitment; H_i = hash_to_field([pi2_i].Marshal(), "BSB22-Plonk").
+ * Transcript: alpha = H("alpha", beta, [pi2_0], .., [z]); v absorbs the Qcp_i(zeta) after the six
+ * evaluations; the linearisation polynomial gains sum_i Qcp_i(zeta) pi2_i(X), the opening at zeta
+ * v^(6+i) Qcp_i(X).  DESIGN.md §3.6. */
+#define ZKMI_PLONK_MAX_COMMITMENTS 8
+typedef struct {
+  uint32_t n_rows;        /* |C_i| >= 1 */
+  uint32_t row;           /* r_i: not in rows */
+  const uint32_t* rows;   /* C_i: n_rows gate rows, ascending, below 2^log_n - 1 */
+  const uint32_t* slots;  /* n_rows value-file slots of the committed operands (wire-backed slots of
+                             the zkmi_cs program, in rows order): what zkmi_plonk_prove_ex reads at the
+                             program's COMMIT row; NULL for a key that only proves from solved wires */
+  const void* lag_g1;     /* n_rows + 2 G1 affine points: [L_g(tau)]_1 for g in rows order, then for
+                             the two blinding rows r_i and 2^log_n - 1 */
+  uint32_t lag_k;         /* bases per subset-sum table of these points, 4 .. 16; 0 = auto */
+} zkmi_plonk_commit_desc;
+/* Attaches the commitments to a key from either loader, before its first prove and once.  The
+ * library builds Qcp_i (coefficient form and coset evaluations) on the GPU and loads the tables of
+ * the Lagrange points.  Refused with a message (csrc/plonk_commit_check.h), nothing attached: n = 0
+ * or above 8, rows not ascending / not unique / outside the domain, row among its own rows, a
+ * blinding row inside C_i, a second call, a call after a prove. */
+int zkmi_plonk_pk_set_commitments(zkmi_ctx* ctx, zkmi_plonk_pk* pk,
+                                  const zkmi_plonk_commit_desc* descs, uint32_t n);
+/* The commitment step alone (a shim's replacement for gnark's bsb22 hint calls it while gnark
+ * solves): values = batch x n_rows fr, blind2 = batch x 2 fr (Montgomery, proof-major) ->
+ * commit_out = batch x 64 bytes ([pi2_index] affine, Montgomery), h_out = batch fr (H, Montgomery). */
+int zkmi_plonk_commit_hint(zkmi_ctx* ctx, zkmi_plonk_pk* pk, uint32_t index, const void* values,
+                           const void* blind2, size_t batch, void* commit_out, void* h_out);
+/* zkmi_plonk_prove / zkmi_plonk_prove_witness for keys with commitments: blind_commit = batch x
+ * 2 n_c fr (per commitment the scalars at r_i and at the last row), commit_out = batch x n_c x 96
+ * bytes ([pi2_i] affine, then Qcp_i(zeta)).  With a key without commitments and both NULL they return
+ * what the plain entries return.  The plain entries and the round-by-round calls refuse a key with
+ * commitments (ZKMI_ERR_ARG).  From inputs, the program's COMMIT rows must be the key's commitments
+ * in order; from solved wires or columns, a proof whose a[r_i] differs from H_i is flagged
+ * ZKMI_ERR_UNSATISFIED. */
+int zkmi_plonk_prove_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_cs* cs, const void* inputs,
+                        size_t batch, const void* blind, const void* blind_commit,
+                        const uint8_t* vk_digest, void* proofs_out, void* commit_out,
+                        int32_t* status_out);
+int zkmi_plonk_prove_witness_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
+                                const void* wires, const void* a, const void* b, const void* c,
+                                size_t n_gates, size_t batch, const void* blind,
+                                const void* blind_commit, const uint8_t* vk_digest, void* proofs_out,
+                                void* commit_out, int32_t* status_out);
+
 /* Per-stage device time of the last zkmi_prove_collect / zkmi_prove_batch in milliseconds, from
  * HIP events on the library's streams: [0] solve (stage 1, second stream), [1] quotient (NTTs +
  * pointwise; with a folded key the transforms of a and b alone), [2] G1 MSMs, [3] G2 MSM, [4] assembly (third stream; overlaps the next batch's

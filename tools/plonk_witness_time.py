@@ -2,7 +2,12 @@
 """Times the gnark drop-in entry of the PLONK prover next to the entries it stands beside, on the
 address circuit (BASELINE config 5: 231 270 gates, domain 2^18), batch 512.  Prints one JSON line.
 
-    python tools/plonk_witness_time.py [--batch 512] [--out FILE]
+    python tools/plonk_witness_time.py [--batch 512] [--workload address|address-commit] [--out FILE]
+
+--workload address-commit: the same circuit with its bytes range-checked through api.Commit
+(circuits.AddressCircuitCommit), proved through zkmi_plonk_prove_ex / zkmi_plonk_prove_witness_ex;
+its wire vectors come from the host evaluation of the program, the commitment hashes from tau
+(plonk.seeded_commit_fn), since the commitment wire depends on the blinding scalars.
 
 Two pairs of numbers, all host clock around calls that end in a stream synchronise:
   key_load   seconds to a resident key: through the trace loader (selectors and permutation to
@@ -36,7 +41,7 @@ LIMIT_S = 540
 DISTINCT = 4
 
 
-def measure(batch):
+def measure(batch, workload="address"):
     import numpy as np
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
     from gnark_crypto_primitives_amd import circuits, lib, plonk, workloads
@@ -45,10 +50,13 @@ def measure(batch):
     from gnark_crypto_primitives_amd.frontend.scs import compile_scs
     from gnark_crypto_primitives_amd.groth16 import g1_gen_mont
     t0 = time.perf_counter()
-    _, gen, _ = workloads.build("address")
-    sc = compile_scs(compile_circuit(circuits.AddressCircuit(), 16))
-    out = {"circuit": "AddressCircuit", "gates": sc.n_gates, "domain_log2": sc.log_n, "batch": batch,
-           "n_wires": sc.wiring()[3], "compile_s": time.perf_counter() - t0}
+    circuit, gen, _ = workloads.build(workload)
+    sc = compile_scs(compile_circuit(circuit, 16))
+    n_c = len(sc.commitments)
+    out = {"circuit": type(circuit).__name__, "gates": sc.n_gates, "domain_log2": sc.log_n,
+           "batch": batch, "n_wires": sc.wiring()[3], "commitments": n_c,
+           "committed_rows": [len(c["rows"]) for c in sc.commitments],
+           "compile_s": time.perf_counter() - t0}
     ctx = lib.Context(0)
 
     def timed(fn):
@@ -79,11 +87,29 @@ def measure(batch):
     ws = [to_mont_array(sc.assignment_vector(gen(rng))) for _ in range(DISTINCT)]
     inp = np.stack([ws[i % DISTINCT] for i in range(batch)])
     blind = np.stack([to_mont_array([rng.randrange(plonk.R) for _ in range(9)]) for _ in range(batch)])
-    abc = np.zeros((3, DISTINCT, sc.n_gates, 4), dtype=np.uint64)
-    status = ctx.solve_batch(prover.cs_h, np.stack(ws), DISTINCT, None, abc)
-    assert not status.any()
-    distinct = sc.wire_vectors(abc[0], abc[1], abc[2])
-    (rec_i, st_i), t_i = median_ms(lambda: prover.prove_raw(inp, blind))
+    extra = {}
+    if n_c:
+        # the commitment wires depend on the blinding scalars: one pair per distinct witness, the
+        # columns from the host evaluation of the program
+        bcs = [[rng.randrange(plonk.R) for _ in range(2 * n_c)] for _ in range(DISTINCT)]
+        extra = {"blind_commit": np.stack([to_mont_array(bcs[i % DISTINCT]) for i in range(batch)])}
+        rows = []
+        for w, bc in zip(ws, bcs):
+            sc.commit_fn = plonk.seeded_commit_fn(sc, 3, bc)
+            vec = [v * pow(1 << 256, -1, plonk.R) % plonk.R
+                   for v in __import__("gnark_crypto_primitives_amd.frontend.compile",
+                                       fromlist=["array_to_ints"]).array_to_ints(w)]
+            _, a, b, c = sc.run_vprogram(vec)
+            assert sc.last_status == 0
+            rows.append(to_mont_array(sc.wire_vectors([a], [b], [c])[0]))
+        sc.commit_fn = None
+        distinct = np.stack(rows)
+    else:
+        abc = np.zeros((3, DISTINCT, sc.n_gates, 4), dtype=np.uint64)
+        status = ctx.solve_batch(prover.cs_h, np.stack(ws), DISTINCT, None, abc)
+        assert not status.any()
+        distinct = sc.wire_vectors(abc[0], abc[1], abc[2])
+    (rec_i, st_i, *cm_i), t_i = median_ms(lambda: prover.prove_raw(inp, blind, *extra.values()))
     lagrange = prover.lagrange
     prover.close()
     # ---- the trace loader, and the same batch from wire vectors in page-locked memory
@@ -107,11 +133,12 @@ def measure(batch):
     for i in range(batch):
         wires[i] = distinct[i % DISTINCT]
     out["wire_bytes_per_batch"] = int(wires.nbytes)
-    (rec_w, st_w), t_w = median_ms(lambda: wp.prove_raw(blind, wires=wires))
+    (rec_w, st_w, *cm_w), t_w = median_ms(lambda: wp.prove_raw(blind, wires=wires, **extra))
     assert not st_w.any() and not st_i.any()
     out["prove"] = {"witness_pinned": t_w, "inputs": t_i,
                     "ratio_witness_to_inputs": t_w["median_ms"] / t_i["median_ms"],
-                    "records_identical": rec_w.tobytes() == rec_i.tobytes()}
+                    "records_identical": rec_w.tobytes() == rec_i.tobytes() and
+                    all(x.tobytes() == y.tobytes() for x, y in zip(cm_w, cm_i))}
     ctx.host_free(wires)
     wp.close()
     ctx.close()
@@ -121,16 +148,18 @@ def measure(batch):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--workload", default="address", choices=("address", "address-commit"))
     ap.add_argument("--child", action="store_true", help="run the measurement in this process")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     if args.child:
-        print("RESULT " + json.dumps(measure(args.batch)), flush=True)
+        print("RESULT " + json.dumps(measure(args.batch, args.workload)), flush=True)
         return 0
     # a fresh child, killed at its limit; nothing more runs on the GPU after a failure
     try:
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--batch",
-                            str(args.batch)], capture_output=True, text=True, timeout=LIMIT_S)
+                            str(args.batch), "--workload", args.workload], capture_output=True,
+                           text=True, timeout=LIMIT_S)
     except subprocess.TimeoutExpired:
         print(json.dumps({"error": f"time limit of {LIMIT_S} s"}))
         return 1
