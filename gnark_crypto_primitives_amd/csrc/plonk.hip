@@ -421,11 +421,12 @@ __device__ __forceinline__ Fr scs_term(uint32_t mark, const Fr& x, const Fr* q) 
   if (mark == SCS_MARK_MINUS_ONE) return neg(x);
   return fmulp(x, *q);
 }
-template <bool CM>
-__global__ __launch_bounds__(256) void scs_gate_kernel(ScsDev s, const Fr* __restrict__ w,
-                                                       Fr* __restrict__ a, Fr* __restrict__ b,
-                                                       Fr* __restrict__ c, Fr* __restrict__ pub,
-                                                       int32_t* __restrict__ st, size_t Bp) {
+// COLS = false (zkmi_scs_solve_batch): the check alone, no column and no public-input stores.
+template <bool CM, bool COLS>
+__device__ __forceinline__ void scs_gate_rows(const ScsDev& s, const Fr* __restrict__ w,
+                                              Fr* __restrict__ a, Fr* __restrict__ b,
+                                              Fr* __restrict__ c, Fr* __restrict__ pub,
+                                              int32_t* __restrict__ st, size_t Bp) {
   const size_t p = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
   const size_t ng = s.n_gates;
   for (uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.y * 4 + (threadIdx.x >> 6)); g < s.n_gates;
@@ -433,9 +434,11 @@ __global__ __launch_bounds__(256) void scs_gate_kernel(ScsDev s, const Fr* __res
     const uint32_t mk = s.marks[g];
     const Fr va = bi_ld(w, s.x[0][g], p, Bp), vb = bi_ld(w, s.x[1][g], p, Bp),
              vc = bi_ld(w, s.x[2][g], p, Bp);
-    bi_st(a, g, p, Bp, va);
-    bi_st(b, g, p, Bp, vb);
-    bi_st(c, g, p, Bp, vc);
+    if (COLS) {
+      bi_st(a, g, p, Bp, va);
+      bi_st(b, g, p, Bp, vb);
+      bi_st(c, g, p, Bp, vc);
+    }
     Fr sum = add(add(scs_term(mk & 3, va, s.sel + g), scs_term((mk >> 2) & 3, vb, s.sel + ng + g)),
                  scs_term((mk >> 4) & 3, vc, s.sel + 2 * ng + g));
     const uint32_t mm = (mk >> 6) & 3;
@@ -443,11 +446,22 @@ __global__ __launch_bounds__(256) void scs_gate_kernel(ScsDev s, const Fr* __res
     if (((mk >> 8) & 3) != SCS_MARK_ZERO) sum = add(sum, s.sel[4 * ng + g]);
     if (g < s.n_public) {
       sum = sub(sum, va);
-      bi_st(pub, g, p, Bp, va);
+      if (COLS) bi_st(pub, g, p, Bp, va);
     }
     if (CM && s.skip[g]) continue;
     if (!sum.is_zero()) st[p] = ZKMI_ERR_UNSATISFIED;
   }
+}
+template <bool CM>
+__global__ __launch_bounds__(256) void scs_gate_kernel(ScsDev s, const Fr* __restrict__ w,
+                                                       Fr* __restrict__ a, Fr* __restrict__ b,
+                                                       Fr* __restrict__ c, Fr* __restrict__ pub,
+                                                       int32_t* __restrict__ st, size_t Bp) {
+  scs_gate_rows<CM, true>(s, w, a, b, c, pub, st, Bp);
+}
+__global__ __launch_bounds__(256) void scs_gate_check_kernel(ScsDev s, const Fr* __restrict__ w,
+                                                             int32_t* __restrict__ st, size_t Bp) {
+  scs_gate_rows<false, false>(s, w, nullptr, nullptr, nullptr, nullptr, st, Bp);
 }
 
 // ---- commitments (api.Commit) -------------------------------------------------------------------------
@@ -1693,10 +1707,12 @@ int zkmi_scs_load(zkmi_ctx* ctx, const zkmi_scs_desc* d, zkmi_scs** out) {
   return ZKMI_OK;
 }
 
+// solver != NULL (zkmi_plonk_round1_scs / zkmi_plonk_prove_scs): scs is the solver's system and the
+// wires are solved on the device from `wires`, which then holds the batch's inputs
 static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs, const void* wires,
                           const void* a, const void* b, const void* c, size_t n_gates, size_t batch,
                           const void* blind, const void* blind_commit, void* commits_out,
-                          int32_t* status_out);
+                          int32_t* status_out, const zkmi_scs_solver* solver = nullptr);
 int zkmi_plonk_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
                               const void* wires, const void* a, const void* b, const void* c,
                               size_t n_gates, size_t batch, const void* blind, void* commits_out,
@@ -1711,7 +1727,7 @@ int zkmi_plonk_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* 
 static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs, const void* wires,
                           const void* a, const void* b, const void* c, size_t n_gates, size_t batch,
                           const void* blind, const void* blind_commit, void* commits_out,
-                          int32_t* status_out) {
+                          int32_t* status_out, const zkmi_scs_solver* solver) {
   ZK_HIP(hipSetDevice(ctx->device));
   int rc;
   if ((rc = require_idle(ctx))) return rc;
@@ -1723,7 +1739,7 @@ static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
     ctx->err = "plonk: batch must be in [1, max_batch]";
     return ZKMI_ERR_ARG;
   }
-  const bool wire_form = scs && wires && !a && !b && !c;
+  const bool wire_form = scs && (wires || (solver && !scs_solver_inputs(solver))) && !a && !b && !c;
   const bool column_form = !scs && !wires && a && b && c;
   if (!wire_form && !column_form) {
     ctx->err = "plonk witness: give either a system and its wires (a = b = c = NULL) or the three "
@@ -1752,6 +1768,10 @@ static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
     ctx->err = "plonk witness: wire vector larger than the 4n work buffer";
     return ZKMI_ERR_ARG;
   }
+  if (solver && scs_solver_inputs(solver) > m) {
+    ctx->err = "plonk solver: more inputs than the 4n work buffer holds";
+    return ZKMI_ERR_ARG;
+  }
   // first prove of this (trace-loaded key, system) pair: the wiring against the key's permutation
   if (scs && !pk->perm.empty() && scs->checked_key != pk->serial) {
     const std::string bad =
@@ -1777,7 +1797,9 @@ static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
   Fr* pub = (Fr*)pk->big[5].p;   // rows 0 .. n_pub - 1: the public inputs, for PI(X) in round 3
   rc = transpose_in(ctx, tbl.p, pk->small[0].p, 9, batch, Bp, 32);
   if (!rc && scs) {
-    rc = stage_rows(ctx, wires, scs->n_wires, batch, Bp, W);
+    // the solver stages its inputs through A, which the gather below overwrites
+    rc = solver ? scs_solver_run(ctx, solver, wires, batch, Bp, A, W, (int32_t*)st)
+                : stage_rows(ctx, wires, scs->n_wires, batch, Bp, W);
     if (!rc) {
       const ScsDev dev{{scs->x[0], scs->x[1], scs->x[2]}, scs->marks, scs->sel, scs->n_gates,
                        scs->n_public, pk->cm_skip};
@@ -1830,6 +1852,9 @@ int zkmi_plonk_prove_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* s
   return zkmi_plonk_prove_witness_ex(ctx, pk, scs, wires, a, b, c, n_gates, batch, blind, nullptr,
                                      vk_digest, proofs_out, nullptr, status_out);
 }
+static int prove_after_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch,
+                                      const std::vector<G1Affine>& abc, const uint8_t* vk_digest,
+                                      void* proofs_out, void* commit_out);
 int zkmi_plonk_prove_witness_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
                                 const void* wires, const void* a, const void* b, const void* c,
                                 size_t n_gates, size_t batch, const void* blind,
@@ -1845,6 +1870,13 @@ int zkmi_plonk_prove_witness_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs
   int rc = round1_witness(ctx, pk, scs, wires, a, b, c, n_gates, batch, blind, blind_commit, abc.data(),
                           status_out);
   if (rc) return rc;
+  return prove_after_round1_witness(ctx, pk, batch, abc, vk_digest, proofs_out, commit_out);
+}
+// rounds 2 .. 5 behind round1_witness
+static int prove_after_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t batch,
+                                      const std::vector<G1Affine>& abc, const uint8_t* vk_digest,
+                                      void* proofs_out, void* commit_out) {
+  int rc;
   // public inputs: column a of rows 0 .. n_public - 1, which round 1 left in big[5]
   const size_t n_pub = pk->n_public;
   std::vector<Fr> pubs(batch * (n_pub ? n_pub : 1));
@@ -1857,6 +1889,74 @@ int zkmi_plonk_prove_witness_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs
     ZK_HIP(hipStreamSynchronize(ctx->stream));
   }
   return prove_after_round1(ctx, pk, batch, pubs, abc, vk_digest, proofs_out, commit_out);
+}
+
+// ---- the gnark-shaped solve (scs_solve.hip) in front of the wire-form path ----------------------------
+static const char* const kNoCommitmentsScs =
+    "plonk: this key carries commitments: the solver entries (zkmi_plonk_round1_scs / "
+    "zkmi_plonk_prove_scs) do not carry them; solve with gnark and use zkmi_plonk_prove_witness_ex";
+int zkmi_scs_solve_batch(zkmi_ctx* ctx, const zkmi_scs_solver* solver, const void* inputs, size_t batch,
+                         void* wires_out, int32_t* status_out) {
+  if (!ctx) return ZKMI_ERR_ARG;
+  ZK_HIP(hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = require_idle(ctx))) return rc;
+  if (batch == 0) return ZKMI_OK;
+  if (!solver || !status_out || (scs_solver_inputs(solver) && !inputs)) {
+    ctx->err = "scs_solve_batch: null argument";
+    return ZKMI_ERR_ARG;
+  }
+  const zkmi_scs* scs = scs_solver_system(solver);
+  const size_t Bp = round_up(batch, 64), n_in = scs_solver_inputs(solver);
+  Staged sw(ctx), sst(ctx);
+  if (wires_out && (rc = sw.out(wires_out, batch * (size_t)scs->n_wires * 32))) return rc;
+  if ((rc = sst.out(status_out, batch * 4))) return rc;
+  void *w, *staged, *st;
+  zkmi_ctx::ProveSet& S = ctx->sets[0];
+  if ((rc = ensure_scratch(ctx, S.slots, (size_t)scs->n_wires * Bp * 32, &w)) ||
+      (rc = ensure_scratch(ctx, S.a, std::max<size_t>(n_in, 1) * Bp * 32, &staged)) ||
+      (rc = ensure_scratch(ctx, S.misc, Bp * 4, &st)))
+    return rc;
+  ZK_HIP(hipMemsetAsync(st, 0, Bp * 4, ctx->stream));
+  if ((rc = scs_solver_run(ctx, solver, inputs, batch, Bp, (Fr*)staged, (Fr*)w, (int32_t*)st))) return rc;
+  const ScsDev dev{{scs->x[0], scs->x[1], scs->x[2]}, scs->marks, scs->sel, scs->n_gates, scs->n_public, nullptr};
+  hipLaunchKernelGGL(scs_gate_check_kernel,
+                     dim3((unsigned)(Bp / 64), (unsigned)std::min<size_t>((scs->n_gates + 3) / 4, 32768)),
+                     dim3(256), 0, ctx->stream, dev, (const Fr*)w, (int32_t*)st, Bp);
+  ZK_HIP(hipGetLastError());
+  if (wires_out && (rc = transpose_out(ctx, w, sw.dev, scs->n_wires, batch, Bp, 32))) return rc;
+  ZK_HIP(hipMemcpyAsync(sst.dev, st, batch * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if ((rc = sw.finish()) || (rc = sst.finish())) return rc;
+  ZK_HIP(hipStreamSynchronize(ctx->stream));
+  return ZKMI_OK;
+}
+int zkmi_plonk_round1_scs(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver* solver,
+                          const void* inputs, size_t batch, const void* blind, void* commits_out,
+                          int32_t* status_out) {
+  if (!ctx) return ZKMI_ERR_ARG;
+  if (!pk || !solver || (scs_solver_inputs(solver) && !inputs)) {
+    ctx->err = "plonk solver: null argument";
+    return ZKMI_ERR_ARG;
+  }
+  if (!pk->commits.empty()) {
+    ctx->err = kNoCommitmentsScs;
+    return ZKMI_ERR_ARG;
+  }
+  return round1_witness(ctx, pk, scs_solver_system(solver), inputs, nullptr, nullptr, nullptr, 0, batch, blind,
+                        nullptr, commits_out, status_out, solver);
+}
+int zkmi_plonk_prove_scs(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver* solver,
+                         const void* inputs, size_t batch, const void* blind, const uint8_t* vk_digest,
+                         void* proofs_out, int32_t* status_out) {
+  if (!ctx) return ZKMI_ERR_ARG;
+  if (!pk || !solver || !blind || !vk_digest || !proofs_out || !status_out || batch == 0) {
+    ctx->err = "plonk_prove_scs: null argument or empty batch";
+    return ZKMI_ERR_ARG;
+  }
+  std::vector<G1Affine> abc(batch * 3);
+  int rc = zkmi_plonk_round1_scs(ctx, pk, solver, inputs, batch, blind, abc.data(), status_out);
+  if (rc) return rc;
+  return prove_after_round1_witness(ctx, pk, batch, abc, vk_digest, proofs_out, nullptr);
 }
 
 // ---- commitments of a key (api.Commit under PLONK; parity with gnark unpinned) ----------------------

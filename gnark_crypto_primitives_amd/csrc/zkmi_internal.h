@@ -288,6 +288,14 @@ void witness_ring_free(zkmi_ctx* ctx);
 // memory) -> batch-inner rows of `dst` on ctx->stream, host memory through the context's pinned ring.
 // Pageable memory has been consumed on return; the rest when the stream has passed the copies.
 int stage_rows(zkmi_ctx* ctx, const void* src, size_t rows, size_t batch, size_t Bp, void* dst);
+// scs_solve.hip: the solver's own copy of its system and its inputs per proof; the solve of a batch on
+// ctx->stream: the caller's inputs (proof-major, host or device) through `staged` [n_inputs][Bp] to
+// their wires in `w` [n_wires][Bp], then every other wire; status[p] is written for a proof that
+// divides by zero and left alone otherwise
+const zkmi_scs* scs_solver_system(const zkmi_scs_solver* s);
+uint32_t scs_solver_inputs(const zkmi_scs_solver* s);
+int scs_solver_run(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs, size_t batch, size_t Bp,
+                   Fr* staged, Fr* w, int32_t* status);
 
 // RAII staging of a caller buffer (host or device) as device memory
 struct Staged {

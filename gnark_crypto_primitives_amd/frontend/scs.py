@@ -153,6 +153,7 @@ class ScsCircuit:
         for i in range(shift):
             row_of[i] = i
         prog = head + prog
+        self._prog, self._row_of = prog, row_of    # program order before scheduling (solver_description)
         self.n_gates = len(gates)
         self.n_constraints = self.n_gates      # rows the solver emits
         self.log_n = max(2, (self.n_gates - 1).bit_length())
@@ -251,6 +252,162 @@ class ScsCircuit:
             cols = [np.array([wire_of[v] for v in col], dtype=np.uint32) for col in self.wires]
             self._wiring = (cols[0], cols[1], cols[2], n_pub + 1 + len(rest))
         return self._wiring
+
+    def solver_description(self):
+        """The gnark-shaped description of the solve (zkmi_scs_solver_desc), in the numbering of
+        ``wiring()``: a dict with ``n_wires``, ``input_wire`` [n_inputs] (0xFFFFFFFF: nothing reads
+        the input), ``instr`` [n_instr, 2] ((0, gate) | (1, hint), the program order before
+        scheduling), and the hint table ``hint_kind``, ``hint_in_ptr``, ``hint_in_wire``,
+        ``hint_in_coef`` (integers), ``hint_out_ptr``, ``hint_out``.  OP_INV becomes InvZero (kind
+        1), OP_BITS of width 0 / 1 NBits (kind 2); the divisions (OP_DIV, OP_BATCHINV + OP_PAIR) are
+        not exported: the kept rows that define their results are gates the solver divides in.  The
+        one exception is an OP_PAIR value without such a row (IsZero's batched inverse-or-zero, whose
+        first gate has a second unknown): it is the InvZero hint it stands for, placed in front of
+        that gate.  Any other hint raises.  A hint operand or output no gate touches gets a wire behind those of
+        ``wiring()``, so ``n_wires`` here may exceed wiring()'s."""
+        if getattr(self, "_solver_desc", None) is not None:
+            return self._solver_desc
+        names = {OP_HIST: "OP_HIST (lookup multiplicities)", OP_HQ: "OP_HQ (a lookup query)",
+                 OP_COMMIT: "OP_COMMIT (api.Commit)", OP_EMUL: "OP_EMUL (the emulated product)",
+                 OP_BXOR: "OP_BXOR (byte xor)", OP_BAND: "OP_BAND (byte and)",
+                 OP_BITS: "OP_BITS with a limb width (limbs)"}
+        n_pub = self.n_public - 1
+        xa, _, _, n_wires = self.wiring()
+        rest = sorted({v for col in self.wires for v in col if v > n_pub})
+        wire_of = {v: v for v in range(n_pub + 1)}
+        wire_of.update({v: n_pub + 1 + i for i, v in enumerate(rest)})
+
+        def wire(v):                                   # a value no gate touches: a wire of its own
+            nonlocal n_wires
+            if v not in wire_of:
+                wire_of[v] = n_wires
+                n_wires += 1
+            return wire_of[v]
+
+        instr, kinds, in_ptr, in_wire, in_coef, out_ptr, outs = [], [], [0], [], [], [0], []
+
+        def hint(kind, a, out_vals):
+            instr.append((1, len(kinds)))
+            kinds.append(kind)
+            in_wire.append(wire(a))
+            in_coef.append(1)
+            in_ptr.append(len(in_wire))
+            outs.extend(wire(v) for v in out_vals)
+            out_ptr.append(len(outs))
+
+        known = set(range(n_pub + 1)) | {v for v, w in self.cc._val_wire.items()
+                                         if 1 <= w <= self.n_inputs}
+        pairs = {}                                     # value of a pending OP_PAIR -> its operand
+        for i, (op, d, a, b) in enumerate(self._prog):
+            if op == OP_ABC:
+                unknown = {v for v in (d, a, b) if v not in known}
+                if len(unknown) > 1:
+                    for v in sorted(unknown & pairs.keys()):
+                        hint(1, pairs.pop(v), [v])
+                instr.append((0, self._row_of[i]))
+                known.update((d, a, b))
+            elif op == OP_INV or (op == OP_BITS and (b >> 16) <= 1):
+                out_vals = [d + j for j in range(1 if op == OP_INV else b & 0xffff)]
+                hint(1 if op == OP_INV else 2, a, out_vals)
+                known.update(out_vals)
+            elif op == OP_PAIR:
+                pairs[d] = a
+            elif op in names:
+                raise ValueError(f"solver_description: the circuit holds {names[op]}, which the "
+                                 "basic hint set (InvZero, NBits) does not cover")
+            # every other op is a gate (its OP_ABC row follows) or a division a gate defines
+        val_of = {}
+        for v, w in self.cc._val_wire.items():
+            if 1 <= w <= self.n_inputs and (w not in val_of or v < val_of[w]):
+                val_of[w] = v
+        input_wire = [wire_of.get(val_of.get(1 + i), 0xFFFFFFFF) for i in range(self.n_inputs)]
+        u32 = lambda x, shape=(-1,): np.array(x, dtype=np.uint32).reshape(shape)
+        self._solver_desc = {
+            "n_wires": n_wires, "input_wire": u32(input_wire), "instr": u32(instr, (-1, 2)),
+            "hint_kind": u32(kinds), "hint_in_ptr": u32(in_ptr), "hint_in_wire": u32(in_wire),
+            "hint_in_coef": list(in_coef), "hint_out_ptr": u32(out_ptr), "hint_out": u32(outs)}
+        return self._solver_desc
+
+    def solve_description(self, desc, inputs):
+        """Plain-Python interpreter of a solver description: the statement of what
+        zkmi_scs_solve_batch computes and the CPU reference of its tests.  One walk over ``instr``
+        with a solved-wire bitmap that starts with the inputs' wires (ONE is not special: its gate
+        solves it).  A gate whose wires are all known is an assertion; otherwise its one unknown u is
+        solved: where u takes no part in the product (qM = 0, or u in neither a nor b),
+        x = -rest / k with k the sum of the linear selectors on u's positions; where u is exactly one
+        of a, b and qM != 0, x = -rest / (k + qM other), a zero divisor flagging the proof.  Hints:
+        InvZero (1 / v, 0 for v = 0) and NBits (output i = bit i of v), v = coef * wire or coef.
+        inputs: n_inputs integers, public first.  Returns (wires, status): desc["n_wires"] integers
+        and 0 or -5 (a zero divisor, or a gate that does not hold)."""
+        xs = [x.tolist() for x in self.wiring()[:3]]
+        n_wires, n_pub = desc["n_wires"], self.n_public - 1
+        w, solved = [0] * n_wires, [False] * n_wires
+        if len(inputs) != len(desc["input_wire"]):
+            raise ValueError(f"expected {len(desc['input_wire'])} inputs, got {len(inputs)}")
+        for v, iw in zip(inputs, desc["input_wire"].tolist()):
+            if iw != 0xFFFFFFFF:
+                w[iw], solved[iw] = int(v) % R, True
+        status, seen = 0, set()
+        kinds, ip, op_ = desc["hint_kind"].tolist(), desc["hint_in_ptr"].tolist(), desc["hint_out_ptr"].tolist()
+        hw, hc, ho = desc["hint_in_wire"].tolist(), desc["hint_in_coef"], desc["hint_out"].tolist()
+        for ii, (kind, idx) in enumerate(desc["instr"].tolist()):
+            if kind == 1:
+                if kinds[idx] not in (1, 2) or ip[idx + 1] - ip[idx] != 1:
+                    raise ValueError(f"instruction {ii}: not an InvZero or NBits hint with one input")
+                t = ip[idx]
+                if hw[t] != 0xFFFFFFFF and not solved[hw[t]]:
+                    raise ValueError(f"instruction {ii}: reads wire {hw[t]}, which is not solved yet")
+                v = hc[t] * (w[hw[t]] if hw[t] != 0xFFFFFFFF else 1) % R
+                o = ho[op_[idx]:op_[idx + 1]]
+                if any(solved[x] for x in o):
+                    raise ValueError(f"instruction {ii}: an output wire is already solved")
+                if kinds[idx] == 1:
+                    w[o[0]] = pow(v, R - 2, R)
+                else:
+                    for j, x in enumerate(o):
+                        w[x] = (v >> j) & 1
+                for x in o:
+                    solved[x] = True
+                continue
+            g = idx
+            if g in seen:
+                raise ValueError(f"instruction {ii}: gate {g} occurs twice")
+            seen.add(g)
+            pos = [xs[0][g], xs[1][g], xs[2][g]]
+            _, _, _, qL, qR, qO, qM, qC = self.gates[g]
+            unknown = {x for x in pos if not solved[x]}
+            if not unknown:
+                continue
+            if len(unknown) > 1:
+                raise ValueError(f"instruction {ii}: gate {g} has two unknown wires")
+            u = unknown.pop()
+            in_a, in_b = pos[0] == u, pos[1] == u
+            k = sum(q for q, x in zip((qL, qR, qO), pos) if x == u) % R
+            rest = (sum(q * w[x] for q, x in zip((qL, qR, qO), pos) if x != u) + qC) % R
+            if g < n_pub:
+                raise ValueError(f"instruction {ii}: public gate {g} has an unknown wire")
+            if qM % R and (in_a or in_b):
+                if in_a and in_b:
+                    raise ValueError(f"instruction {ii}: gate {g} is quadratic in its unknown")
+                den = (k + qM * w[pos[1] if in_a else pos[0]]) % R
+                if den == 0:
+                    status = -5
+                w[u] = -rest * pow(den, R - 2, R) % R
+            else:
+                if k == 0:
+                    raise ValueError(f"instruction {ii}: the unknown of gate {g} has coefficient 0")
+                rest = (rest + qM * w[pos[0]] * w[pos[1]]) % R
+                w[u] = -rest * pow(k, R - 2, R) % R
+            solved[u] = True
+        if len(seen) != self.n_gates:
+            raise ValueError("a gate occurs in no instruction")
+        if not all(solved):
+            raise ValueError(f"wire {solved.index(False)} is still unsolved")
+        for g, (_, _, _, qL, qR, qO, qM, qC) in enumerate(self.gates):
+            a, b, c = w[xs[0][g]], w[xs[1][g]], w[xs[2][g]]
+            if (qL * a + qR * b + qO * c + qM * a * b + qC - (a if g < n_pub else 0)) % R:
+                status = -5
+        return w, status
 
     def wire_vectors(self, a, b, c):
         """Solved columns -> the wire vectors zkmi_plonk_prove_witness takes (scs != NULL form): wire

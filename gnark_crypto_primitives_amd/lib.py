@@ -75,6 +75,14 @@ class ScsDesc(C.Structure):
                 ("selectors", C.c_void_p)]
 
 
+class ScsSolverDesc(C.Structure):
+    _fields_ = [("n_inputs", C.c_uint32), ("input_wire", C.c_void_p), ("n_instr", C.c_uint32),
+                ("n_hints", C.c_uint32), ("instr", C.c_void_p), ("hint_kind", C.c_void_p),
+                ("hint_in_ptr", C.c_void_p), ("hint_in_wire", C.c_void_p),
+                ("hint_in_coef", C.c_void_p), ("hint_out_ptr", C.c_void_p), ("hint_out", C.c_void_p),
+                ("lanes_per_proof", C.c_uint32), ("hint_set", C.c_uint32)]
+
+
 class PlonkCommitDesc(C.Structure):
     _fields_ = [("n_rows", C.c_uint32), ("row", C.c_uint32), ("rows", C.c_void_p),
                 ("slots", C.c_void_p), ("lag_g1", C.c_void_p), ("lag_k", C.c_uint32)]
@@ -150,6 +158,12 @@ SYMBOLS = [
     ("zkmi_plonk_prove_ex", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     ("zkmi_plonk_prove_witness_ex", _I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _P, _P, _P, _P, _P,
                                          _P]),
+    ("zkmi_scs_solver_load", _I, [_P, _P, C.POINTER(ScsSolverDesc), C.POINTER(_P)]),
+    ("zkmi_scs_solver_free", None, [_P, _P]),
+    ("zkmi_scs_solver_info", _I, [_P, C.POINTER(C.c_uint64)]),
+    ("zkmi_scs_solve_batch", _I, [_P, _P, _P, _SZ, _P, _P]),
+    ("zkmi_plonk_round1_scs", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P]),
+    ("zkmi_plonk_prove_scs", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
 ]
 
 _lib = None
@@ -429,6 +443,29 @@ class Context:
 
     def scs_free(self, h):
         self.lib.zkmi_scs_free(self.h, h)
+
+    def scs_solver_load(self, scs_h, desc: "ScsSolverDesc"):
+        h = C.c_void_p()
+        self._check(self.lib.zkmi_scs_solver_load(self.h, scs_h, C.byref(desc), C.byref(h)),
+                    "zkmi_scs_solver_load")
+        return h
+
+    def scs_solver_free(self, h):
+        self.lib.zkmi_scs_solver_free(self.h, h)
+
+    def scs_solver_info(self, h):
+        arr = (C.c_uint64 * 8)()
+        self._check(self.lib.zkmi_scs_solver_info(h, arr), "zkmi_scs_solver_info")
+        return dict(zip(("n_instr", "lanes_per_proof", "n_records", "n_steps", "n_inversions",
+                         "n_wires", "n_gates", "n_inputs"), [int(x) for x in arr]))
+
+    def scs_solve_batch(self, solver_h, inputs, batch, wires_out=None, status_out=None):
+        if status_out is None:
+            status_out = np.zeros(batch, dtype=np.int32)
+        self._check(self.lib.zkmi_scs_solve_batch(self.h, solver_h, _ptr(inputs), batch,
+                                                  _ptr(wires_out), _ptr(status_out)),
+                    "zkmi_scs_solve_batch")
+        return status_out
 
     def host_alloc(self, shape, dtype=np.uint64):
         """numpy array over page-locked memory from zkmi_host_alloc (free with host_free)."""

@@ -539,7 +539,7 @@ class WitnessProver:
                 self._keep += [order, pts]
                 lag_g1[c] = pts.ctypes.data
                 lag_rows[c] = order.ctypes.data
-        self.pk_h = self.scs_h = None
+        self.pk_h = self.scs_h = self.solver_h = None
         self.pk_h = ctx.plonk_pk_load_trace(_lib.PlonkTraceDesc(
             pk.log_n, pk.n_public, sel.ctypes.data, perm.ctypes.data, srs.ctypes.data, window_bits,
             max_batch, lag_g1, lag_rows, lag_k))
@@ -556,11 +556,74 @@ class WitnessProver:
         if getattr(self, "scs_h", None):
             self.ctx.scs_free(self.scs_h)
             self.scs_h = None
+        if getattr(self, "solver_h", None):
+            self.ctx.scs_solver_free(self.solver_h)
+            self.solver_h = None
 
     proofs_of = staticmethod(Prover.proofs_of)
 
-    def _args(self, blind, wires, columns):
+    def load_solver(self, lanes_per_proof=0, desc=None):
+        """The gnark-shaped solver of the system (zkmi_scs_solver_load): ``prove_raw(blind,
+        inputs=...)`` and ``solve`` then need no host solver.  desc: what
+        ``ScsCircuit.solver_description()`` returns (the system's own by default).  The description
+        may number wires behind those of ``wiring()`` (hint operands no gate touches): the solver
+        gets the system with that many wires.  Replaces a solver loaded before; returns its handle."""
+        ctx, system = self.ctx, self.system
+        d = system.solver_description() if desc is None else desc
+        n_wires = int(d["n_wires"])
+        if n_wires < self.n_wires:
+            raise ValueError("the description has fewer wires than the system")
+        u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)
+        coef = to_mont_array([int(c) % R for c in d["hint_in_coef"]]) if len(d["hint_in_coef"]) \
+            else np.zeros((0, 4), np.uint64)
+        arrs = [u32(d[k]) for k in ("input_wire", "instr", "hint_kind", "hint_in_ptr", "hint_in_wire")]
+        arrs += [np.ascontiguousarray(coef), u32(d["hint_out_ptr"]), u32(d["hint_out"])]
+        sd = _lib.ScsSolverDesc(len(arrs[0]), arrs[0].ctypes.data, arrs[1].size // 2, len(arrs[2]),
+                                *[a.ctypes.data for a in arrs[1:]], lanes_per_proof, 0)
+        scs_h = self.scs_h
+        if n_wires != self.n_wires:
+            sel = np.ascontiguousarray(self._keep[0][:, :self.n_gates])
+            xs = [u32(x) for x in system.wiring()[:3]]
+            scs_h = ctx.scs_load(_lib.ScsDesc(n_wires, self.n_gates, self.pk.n_public,
+                                              *[x.ctypes.data for x in xs], sel.ctypes.data))
+        try:
+            h = ctx.scs_solver_load(scs_h, sd)
+        finally:
+            if scs_h is not self.scs_h:
+                ctx.scs_free(scs_h)
+        if self.solver_h:
+            ctx.scs_solver_free(self.solver_h)
+        self.solver_h, self.solver_wires, self.n_inputs = h, n_wires, len(arrs[0])
+        return h
+
+    def _inputs(self, inputs):
+        if not self.solver_h:
+            raise ValueError("load_solver() first")
+        if inputs.ndim != 3 or tuple(inputs.shape[1:]) != (self.n_inputs, 4):
+            raise ValueError("inputs must be [batch, n_inputs, 4]")
+        return np.ascontiguousarray(inputs) if isinstance(inputs, np.ndarray) else inputs
+
+    def solve(self, inputs):
+        """zkmi_scs_solve_batch: inputs [batch, n_inputs, 4] (Montgomery, public first) -> (status
+        [batch], wires [batch, n_wires of the description, 4]); the first ``n_wires`` of the system
+        are what ``prove_raw(blind, wires=...)`` takes."""
+        inputs = self._inputs(inputs)
+        batch = inputs.shape[0]
+        wires = np.zeros((batch, self.solver_wires, 4), dtype=np.uint64)
+        status = self.ctx.scs_solve_batch(self.solver_h, inputs, batch, wires)
+        return status, wires
+
+    def _args(self, blind, wires, columns, inputs=None):
         """(batch, the seven witness arguments of the C entry, public inputs as an array)"""
+        if inputs is not None:
+            if wires is not None or columns is not None:
+                raise ValueError("give one of wires, columns, inputs")
+            inputs = self._inputs(inputs)
+            batch = inputs.shape[0]
+            if tuple(blind.shape) != (batch, 9, 4):
+                raise ValueError("blind must be [batch, 9, 4]")
+            host = inputs if isinstance(inputs, np.ndarray) else inputs.cpu().numpy()
+            return batch, inputs, host[:, :self.pk.n_public]
         if (wires is None) == (columns is None):
             raise ValueError("give either wires or columns")
         n_pub = self.pk.n_public
@@ -583,18 +646,25 @@ class WitnessProver:
             raise ValueError("blind must be [batch, 9, 4]")
         return batch, wit, pubs
 
-    def prove_raw(self, blind, wires=None, columns=None, blind_commit=None):
-        """plonk.Prove through zkmi_plonk_prove_witness.  wires: [batch, n_wires, 4] (Montgomery; a
+    def prove_raw(self, blind, wires=None, columns=None, blind_commit=None, inputs=None):
+        """plonk.Prove through zkmi_plonk_prove_witness, or, with inputs = [batch, n_inputs, 4]
+        (Montgomery, public first, as Prover.prove_raw takes them) and after load_solver(), through
+        zkmi_plonk_prove_scs: the wires are solved on the GPU.  wires: [batch, n_wires, 4] (Montgomery; a
         numpy array, pageable or from Context.host_alloc, or a device tensor); or columns = (a, b,
         c), [batch, n_gates, 4] each, taken as they are.  Returns (records, status) as
         Prover.prove_raw does; for a key with commitments, with blind_commit, (records, status,
         commit records) through zkmi_plonk_prove_witness_ex."""
-        batch, wit, _ = self._args(blind, wires, columns)
+        batch, wit, _ = self._args(blind, wires, columns, inputs)
         blind = np.ascontiguousarray(blind)
         rec = np.zeros((batch, 96), dtype=np.uint64)
         status = np.zeros(batch, dtype=np.int32)
         vkd = (C.c_uint8 * 32).from_buffer_copy(self.pk.vk_digest)
         n_c = len(self.pk.commitments)
+        if inputs is not None:
+            self.ctx._check(self.ctx.lib.zkmi_plonk_prove_scs(
+                self.ctx.h, self.pk_h, self.solver_h, _lib._ptr(wit), batch, blind.ctypes.data, vkd,
+                rec.ctypes.data, status.ctypes.data), "zkmi_plonk_prove_scs")
+            return rec, status
         if n_c:
             blind_commit = _blind_commit(blind_commit, batch, n_c)
             cm = np.zeros((batch, n_c, 12), dtype=np.uint64)
@@ -607,20 +677,26 @@ class WitnessProver:
             status.ctypes.data), "zkmi_plonk_prove_witness")
         return rec, status
 
-    def prove(self, blind, wires=None, columns=None):
-        """The round-by-round twin of prove_raw: zkmi_plonk_round1_witness, then Prover.prove's
-        rounds and Python transcript.  Returns (list of Proof, status)."""
+    def prove(self, blind, wires=None, columns=None, inputs=None):
+        """The round-by-round twin of prove_raw: zkmi_plonk_round1_witness (inputs:
+        zkmi_plonk_round1_scs), then Prover.prove's rounds and Python transcript.  Returns (list of
+        Proof, status)."""
         ctx = self.ctx
         if self.pk.commitments:
             raise ValueError("a key with commitments proves through prove_raw only: the "
                              "round-by-round calls do not carry them")
-        batch, wit, pubs = self._args(blind, wires, columns)
+        batch, wit, pubs = self._args(blind, wires, columns, inputs)
         blind = np.ascontiguousarray(blind)
         rinv = pow(1 << 256, R - 2, R)
         pubs = [[v * rinv % R for v in array_to_ints(np.ascontiguousarray(pubs[i]))]
                 if self.pk.n_public else [] for i in range(batch)]
 
         def round1(c_abc, status):
+            if inputs is not None:
+                ctx._check(ctx.lib.zkmi_plonk_round1_scs(
+                    ctx.h, self.pk_h, self.solver_h, _lib._ptr(wit), batch, blind.ctypes.data,
+                    c_abc.ctypes.data, status.ctypes.data), "zkmi_plonk_round1_scs")
+                return
             ctx._check(ctx.lib.zkmi_plonk_round1_witness(
                 ctx.h, self.pk_h, *wit, batch, blind.ctypes.data, c_abc.ctypes.data,
                 status.ctypes.data), "zkmi_plonk_round1_witness")

@@ -662,6 +662,59 @@ int zkmi_plonk_prove_witness_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs
                                 const void* blind_commit, const uint8_t* vk_digest, void* proofs_out,
                                 void* commit_out, int32_t* status_out);
 
+/* -- PLONK: solve a gnark-shaped SparseR1CS on the GPU from inputs ----------------------------------- */
+/* The third PLONK entry, the twin of zkmi_r1cs_solver_load / zkmi_prove_r1cs_submit: the caller holds
+ * gnark's sparse system (zkmi_scs_load), its instruction order and its hints, and no witness program
+ * of this repository's frontend; spr.Solve runs on the GPU.  The caller names no solve wire: the
+ * loader walks `instr` once with a solved-wire bitmap that starts with the wires of input_wire (the
+ * ONE wire is not special, its gate qL x - 1 = 0 solves it) and finds each gate's one unknown
+ * (csrc/scs_plan.h).  A hint input is a single term, coef * wire or a constant,
+ * because a variable of gnark's scs builder is a single term [UPSTREAM-RECALL]; parity unpinned.
+ * Hints: ZKMI_HINT_INVZERO and ZKMI_HINT_NBITS; kinds 3 .. 7 are refused by name. */
+typedef struct {
+  uint32_t n_inputs;            /* values per proof, public first: the inputs of zkmi_plonk_prove */
+  const uint32_t* input_wire;   /* n_inputs: wire each input lands on; 0xFFFFFFFF = no gate reads it */
+  uint32_t n_instr, n_hints;
+  const uint32_t* instr;        /* n_instr x 2: (0 = gate | 1 = hint, index), solve order; every gate once */
+  const uint32_t* hint_kind;    /* n_hints: enum zkmi_hint_kind */
+  const uint32_t* hint_in_ptr;  /* n_hints + 1 */
+  const uint32_t* hint_in_wire; /* per hint input: a wire, or 0xFFFFFFFF for a constant */
+  const void*     hint_in_coef; /* per hint input: fr, Montgomery: value = coef * wire, or coef alone */
+  const uint32_t* hint_out_ptr; /* n_hints + 1 */
+  const uint32_t* hint_out;
+  uint32_t lanes_per_proof;     /* power of two 1..64; 0 = auto */
+  uint32_t hint_set;            /* 0 = ZKMI_HINTS_BASIC; anything else refused, naming the field.  The
+                                   last field: it takes the values a later hint set defines */
+} zkmi_scs_solver_desc;
+typedef struct zkmi_scs_solver zkmi_scs_solver;
+/* Builds and checks the solve plan on the host and uploads it with a copy of the system; the system
+ * and the caller's arrays (host memory) may be freed afterwards.  ZKMI_ERR_ARG with a message that
+ * names the instruction for whatever the plan refuses (csrc/scs_plan.h lists it); nothing is loaded
+ * then. */
+int zkmi_scs_solver_load(zkmi_ctx* ctx, const zkmi_scs* scs, const zkmi_scs_solver_desc* desc,
+                         zkmi_scs_solver** out);
+void zkmi_scs_solver_free(zkmi_ctx* ctx, zkmi_scs_solver* solver);
+/* info: [0] instructions, [1] lanes per proof, [2] solve records, [3] steps, [4] inversions per
+ * proof, [5] n_wires, [6] n_gates, [7] inputs per proof. */
+int zkmi_scs_solver_info(const zkmi_scs_solver* solver, uint64_t* info /* 8 */);
+/* The witness solve alone: inputs = batch x n_inputs fr (Montgomery, proof-major, host or device) ->
+ * wires_out = batch x n_wires fr (may be NULL), status_out = per proof 0 or ZKMI_ERR_UNSATISFIED (a
+ * solve divides by zero, or a gate does not hold: every gate is checked afterwards, so the status is
+ * what zkmi_plonk_prove_witness reports for the same wires). */
+int zkmi_scs_solve_batch(zkmi_ctx* ctx, const zkmi_scs_solver* solver, const void* inputs, size_t batch,
+                         void* wires_out, int32_t* status_out);
+/* zkmi_plonk_round1_witness / zkmi_plonk_prove_witness (wire form) with the wires solved on the GPU
+ * from the inputs: same columns, same transcript, same records.  Refused before anything is queued:
+ * a key with commitments, an n_public that differs from the key's, batch outside [1, max_batch], more
+ * wires than the 4n work buffer holds and, for a trace-loaded key, a wiring that contradicts the
+ * key's permutation. */
+int zkmi_plonk_round1_scs(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver* solver,
+                          const void* inputs, size_t batch, const void* blind, void* commits_out,
+                          int32_t* status_out);
+int zkmi_plonk_prove_scs(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver* solver,
+                         const void* inputs, size_t batch, const void* blind, const uint8_t* vk_digest,
+                         void* proofs_out, int32_t* status_out);
+
 /* Per-stage device time of the last zkmi_prove_collect / zkmi_prove_batch in milliseconds, from
  * HIP events on the library's streams: [0] solve (stage 1, second stream), [1] quotient (NTTs +
  * pointwise; with a folded key the transforms of a and b alone), [2] G1 MSMs, [3] G2 MSM, [4] assembly (third stream; overlaps the next batch's

@@ -3,6 +3,13 @@
 address circuit (BASELINE config 5: 231 270 gates, domain 2^18), batch 512.  Prints one JSON line.
 
     python tools/plonk_witness_time.py [--batch 512] [--workload address|address-commit] [--out FILE]
+                                       [--entry scs]
+
+--entry scs: a third leg behind the two, on the trace-loaded key: the gnark-shaped solver
+(zkmi_scs_solver_load) for every lane count 1 .. 64 and the automatic one -- the plan's records,
+steps and inversions, and the solve alone (zkmi_scs_solve_batch without the wires copied out) -- then
+one batch through zkmi_plonk_prove_scs with the automatic lane count; the records of the three
+entries must be identical.  Keys without commitments only.
 
 --workload address-commit: the same circuit with its bytes range-checked through api.Commit
 (circuits.AddressCircuitCommit), proved through zkmi_plonk_prove_ex / zkmi_plonk_prove_witness_ex;
@@ -41,7 +48,7 @@ LIMIT_S = 540
 DISTINCT = 4
 
 
-def measure(batch, workload="address"):
+def measure(batch, workload="address", entry=None):
     import numpy as np
     import torch  # noqa: F401  (before the library: one HIP runtime per process)
     from gnark_crypto_primitives_amd import circuits, lib, plonk, workloads
@@ -140,6 +147,27 @@ def measure(batch, workload="address"):
                     "records_identical": rec_w.tobytes() == rec_i.tobytes() and
                     all(x.tobytes() == y.tobytes() for x, y in zip(cm_w, cm_i))}
     ctx.host_free(wires)
+    if entry == "scs":
+        if n_c:
+            raise SystemExit("--entry scs: the solver entries do not carry commitments")
+        t = time.perf_counter()
+        desc = sc.solver_description()
+        leg = {"description_s": time.perf_counter() - t, "n_wires": int(desc["n_wires"]),
+               "n_hints": int(len(desc["hint_kind"])), "lanes": {}}
+        for lanes in (1, 2, 4, 8, 16, 32, 64, 0):
+            t = time.perf_counter()
+            h = wp.load_solver(lanes)
+            load_s = time.perf_counter() - t
+            info = ctx.scs_solver_info(h)
+            st_s, t_s = median_ms(lambda: ctx.scs_solve_batch(h, inp, batch))
+            assert not st_s.any()
+            leg["lanes"]["auto" if lanes == 0 else str(lanes)] = dict(info, load_s=load_s, solve=t_s)
+        (rec_s, st_s), t_p = median_ms(lambda: wp.prove_raw(blind, inputs=inp))
+        assert not st_s.any()
+        assert rec_s.tobytes() == rec_i.tobytes() == rec_w.tobytes(), "the three entries disagree"
+        leg["prove"] = t_p
+        leg["records_identical"] = True
+        out["scs"] = leg
     wp.close()
     ctx.close()
     return out
@@ -149,19 +177,22 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--workload", default="address", choices=("address", "address-commit"))
+    ap.add_argument("--entry", default=None, choices=("scs",), help="also time the solver entry")
     ap.add_argument("--child", action="store_true", help="run the measurement in this process")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     if args.child:
-        print("RESULT " + json.dumps(measure(args.batch, args.workload)), flush=True)
+        print("RESULT " + json.dumps(measure(args.batch, args.workload, args.entry)), flush=True)
         return 0
     # a fresh child, killed at its limit; nothing more runs on the GPU after a failure
+    limit = LIMIT_S + (300 if args.entry else 0)     # the third leg: eight plans, 36 more batches
     try:
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--batch",
-                            str(args.batch), "--workload", args.workload], capture_output=True,
-                           text=True, timeout=LIMIT_S)
+                            str(args.batch), "--workload", args.workload] +
+                           (["--entry", args.entry] if args.entry else []), capture_output=True,
+                           text=True, timeout=limit)
     except subprocess.TimeoutExpired:
-        print(json.dumps({"error": f"time limit of {LIMIT_S} s"}))
+        print(json.dumps({"error": f"time limit of {limit} s"}))
         return 1
     lines = [x for x in p.stdout.splitlines() if x.startswith("RESULT ")]
     if p.returncode != 0 or not lines:
