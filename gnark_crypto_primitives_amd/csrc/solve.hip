@@ -156,21 +156,43 @@ __device__ __forceinline__ Fr ld_sel(const Fr* slots, const Fr* consts, uint32_t
   return r;
 }
 
-template <int S, bool EMUL>
-__global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict__ prog,
-                                                        const Fr* __restrict__ consts, Fr* slots,
-                                                        Fr* __restrict__ a, Fr* __restrict__ b,
-                                                        Fr* __restrict__ c,
-                                                        int32_t* __restrict__ status, size_t Bp,
-                                                        uint32_t n_rows, uint32_t row_begin,
-                                                        uint32_t row_end) {
+// Program chunk of a wavefront in LDS: CH rows of 1 + S quads (see the body).  Fewer rows per chunk
+// for 32 and 64 sub-lanes: the chunk stays ~520 quads, nine prefetch registers.
+template <int S>
+struct SolveChunk {
+  static constexpr uint32_t CH = S > 32 ? 8 : S > 16 ? 16 : 32, RQ = 1 + S, CQ = CH * RQ,
+                            NX = (CQ + 63) / 64;
+};
+
+// One wavefront's solve: 64 / S proofs, lane tl of wavefront `wave` of the launch, pq the wavefront's
+// own CQ quads of LDS.  MAXW: the launch bound in wavefronts; above 1 the wavefront shares its
+// workgroup with others (below).  At MAXW = 8 a wave has 256 registers, which the compiler splits
+// 128 + 128 for a kernel that names accumulation registers, and then allocates values of its own to
+// a0..a31 as well: the untracked stores of st_acc would not be safe there, so those instances store
+// from VGPRs with ordinary, compiler-tracked stores and name no accumulation register at all.
+template <int S, bool EMUL, int MAXW>
+__device__ __forceinline__ void solve_vliw_wave(
+    uint4* const pq, const uint32_t tl, const size_t wave, const uint4* __restrict__ prog,
+    const Fr* __restrict__ consts, Fr* slots, Fr* __restrict__ a, Fr* __restrict__ b,
+    Fr* __restrict__ c, int32_t* __restrict__ status, size_t Bp, uint32_t n_rows, uint32_t row_begin,
+    uint32_t row_end) {
   constexpr int PPW = 64 / S;   // proofs per wavefront
-  const uint32_t sl = threadIdx.x / PPW;   // sub-lane
-  const size_t lane = (size_t)blockIdx.x * PPW + (threadIdx.x % PPW);   // proof
+  constexpr bool PACKED = MAXW > 1, ACC = MAXW <= 4;
+  const uint32_t sl = tl / PPW;   // sub-lane
+  const size_t lane = wave * PPW + (tl % PPW);   // proof
   int32_t st = 0;
 #define LD(i) bi_ld(slots, (i), lane, Bp)
 #define ST(i, v) bi_st(slots, (i), lane, Bp, (v))
-#define STA(i, v) st_acc<0, true, false>(slots, (i), lane, Bp, (v))
+#define STR(BANK, WAIT, NT, base, row, v)                          \
+  do {                                                               \
+    if constexpr (ACC)                                               \
+      st_acc<BANK, WAIT, NT>((base), (row), lane, Bp, (v));          \
+    else if constexpr (NT)                                           \
+      bi_st_nt((base), (row), lane, Bp, (v));                        \
+    else                                                             \
+      bi_st((base), (row), lane, Bp, (v));                           \
+  } while (0)
+#define STA(i, v) STR(0, true, false, slots, (i), (v))
 #define LDSEL(i, isc) ld_sel(slots, consts, (i), (isc), lane, Bp)
   // Program rows reach the lanes through LDS, a chunk of CH rows at a time: the next chunk is
   // loaded into registers while the current one runs and written to LDS at the chunk boundary.
@@ -179,9 +201,8 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
   // name the load -- which also waits for the previous step's STORES to be acknowledged before the
   // operand loads can even be issued: one L2 round trip per step on the critical path.  LDS reads
   // count on lgkmcnt, so the operand loads now follow the stores back to back.
-  // (fewer rows per chunk for 32 and 64 sub-lanes: the chunk stays ~520 quads, nine prefetch registers)
-  constexpr uint32_t CH = S > 32 ? 8 : S > 16 ? 16 : 32, RQ = 1 + S, CQ = CH * RQ, NX = (CQ + 63) / 64;
-  __shared__ uint4 pq[CQ];
+  constexpr uint32_t CH = SolveChunk<S>::CH, RQ = SolveChunk<S>::RQ, CQ = SolveChunk<S>::CQ,
+                     NX = SolveChunk<S>::NX;
   const uint32_t total_q = n_rows * RQ;
   uint4 nx[NX];
   uint32_t cur = 0xffffffffu, pre = 0xffffffffu;   // chunk in LDS / chunk in nx (wave-uniform)
@@ -191,23 +212,31 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
       if (ci != pre) {
 #pragma unroll
         for (uint32_t i = 0; i < NX; i++) {
-          const uint32_t o = i * 64 + threadIdx.x, gq = ci * CQ + o;
+          const uint32_t o = i * 64 + tl, gq = ci * CQ + o;
           nx[i] = (o < CQ && gq < total_q) ? prog[gq] : make_uint4(0, 0, 0, 0);
         }
       }
 #pragma unroll
       for (uint32_t i = 0; i < NX; i++) {
-        const uint32_t o = i * 64 + threadIdx.x;
+        const uint32_t o = i * 64 + tl;
         if (o < CQ) pq[o] = nx[i];
       }
       cur = ci;
       pre = ci + 1;
 #pragma unroll
       for (uint32_t i = 0; i < NX; i++) {
-        const uint32_t o = i * 64 + threadIdx.x, gq = pre * CQ + o;
+        const uint32_t o = i * 64 + tl, gq = pre * CQ + o;
         nx[i] = (o < CQ && gq < total_q) ? prog[gq] : make_uint4(0, 0, 0, 0);
       }
-      __syncthreads();   // one wavefront per workgroup: orders the LDS writes before the reads
+      // Orders the LDS writes before the reads.  Only this wavefront touches its slice and the LDS
+      // serves a wavefront's accesses in issue order, so with several waves in the workgroup the
+      // compiler alone has to be held: no s_barrier, the waves stay independent.
+      if constexpr (!PACKED) {
+        __syncthreads();   // one wavefront per workgroup
+      } else {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
     }
     const uint32_t rr = r - ci * CH;
     const uint4 q = pq[(r - ci * CH) * RQ + 1 + sl];
@@ -231,9 +260,9 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
           if (fma) vc = add(vc, vz);
           STA(d, vc);
           if (op == OP_MULABC) {
-            st_acc<1, false, true>(a, k, lane, Bp, va);
-            st_acc<2, false, true>(b, k, lane, Bp, vb);
-            st_acc<3, false, true>(c, k, lane, Bp, vc);
+            STR(1, false, true, a, k, va);
+            STR(2, false, true, b, k, vb);
+            STR(3, false, true, c, k, vc);
           }
         }
         break;
@@ -244,9 +273,9 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
           const Fr ab2 = add(ab, ab);
           STA(d, sub(add(va, vb), ab2));
           if (op == OP_XORABC) {   // OP_XOR: value only (PLONK lowering: rows come from OP_ABC)
-            st_acc<1, false, true>(a, k, lane, Bp, add(va, va));
-            st_acc<2, false, true>(b, k, lane, Bp, vb);
-            st_acc<3, false, true>(c, k, lane, Bp, ab2);
+            STR(1, false, true, a, k, add(va, va));
+            STR(2, false, true, b, k, vb);
+            STR(3, false, true, c, k, ab2);
           }
         }
         break;
@@ -273,9 +302,9 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
       case CLS_R:
         if (op != OP_END) {
           const Fr va = LD(d), vb = LD(x), vc = LD(y);
-          st_acc<1, true, true>(a, k, lane, Bp, va);
-          st_acc<2, false, true>(b, k, lane, Bp, vb);
-          st_acc<3, false, true>(c, k, lane, Bp, vc);
+          STR(1, true, true, a, k, va);
+          STR(2, false, true, b, k, vb);
+          STR(3, false, true, c, k, vc);
           if (vq_assert(q.x) && fmul(va, vb) != vc) st = ZKMI_ERR_UNSATISFIED;
         }
         break;
@@ -439,9 +468,53 @@ __global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict_
 #undef LD
 #undef ST
 #undef STA
+#undef STR
 #undef LDSEL
   // a proof is unsatisfied if any of its sub-lanes saw a failing row
   if (st) atomicMin(&status[lane], st);
+}
+
+// One wavefront per workgroup.
+template <int S, bool EMUL>
+__global__ __launch_bounds__(64) void solve_vliw_kernel(const uint4* __restrict__ prog,
+                                                        const Fr* __restrict__ consts, Fr* slots,
+                                                        Fr* __restrict__ a, Fr* __restrict__ b,
+                                                        Fr* __restrict__ c,
+                                                        int32_t* __restrict__ status, size_t Bp,
+                                                        uint32_t n_rows, uint32_t row_begin,
+                                                        uint32_t row_end) {
+  __shared__ uint4 pq[SolveChunk<S>::CQ];
+  solve_vliw_wave<S, EMUL, 1>(pq, threadIdx.x, blockIdx.x, prog, consts, slots, a, b, c, status,
+                                  Bp, n_rows, row_begin, row_end);
+}
+
+// blockDim.x / 64 = 2, 4 or 8 wavefronts per workgroup, `waves` in the launch.  The wavefronts of a
+// workgroup share nothing: each has its own slice of the LDS chunk and never meets the others at a
+// barrier.  What the workgroup buys is placement: the dispatcher spreads one-wave workgroups
+// over as many CUs as there are waves, and every SIMD that holds a solve wave (150 + 32 registers,
+// 184 of 512 allocated) has room for two instead of four waves of a 128-register kernel beside
+// it -- the 256-thread blocks of the MSM accumulate need a slot on all four SIMDs, so the whole
+// CU drops from four resident blocks to two.  Four to a workgroup, the 128 waves of a 1024-proof
+// batch at S = 8 sit on 32 CUs, one to a SIMD, and the other 224 keep full occupancy: the G1 stage
+// beside the solve fell from 76.2 to 70.7 ms per step.
+// MAXW = 4 (blocks of 2 or 4 waves) or 8: the launch bound.  Up to one wave per SIMD the register
+// budget is the one-wave kernel's and so is the allocation.  Two waves per SIMD leave 256 registers
+// (see solve_vliw_wave: no accumulation registers there), and two latency chains share each SIMD:
+// the solve runs a quarter longer, which is why 8 is not the default.  (Sixteen would need
+// 4 x 184 registers per SIMD: not resident, refused by the host.)
+// The LDS is sized statically, MAXW slices: with dynamic LDS the compiler no longer moves the
+// dynamically indexed element of the bit-decomposition arms to LDS and it lands in scratch.
+template <int S, bool EMUL, int MAXW>
+__global__ __launch_bounds__(64 * MAXW) void solve_vliw_packed_kernel(
+    const uint4* __restrict__ prog, const Fr* __restrict__ consts, Fr* slots, Fr* __restrict__ a,
+    Fr* __restrict__ b, Fr* __restrict__ c, int32_t* __restrict__ status, size_t Bp, uint32_t n_rows,
+    uint32_t row_begin, uint32_t row_end, uint32_t waves) {
+  __shared__ uint4 pq_all[MAXW][SolveChunk<S>::CQ];
+  const uint32_t wv = threadIdx.x / 64;
+  const uint32_t wave = blockIdx.x * (blockDim.x / 64) + wv;
+  if (wave >= waves) return;   // the last workgroup's spare wavefronts
+  solve_vliw_wave<S, EMUL, MAXW>(pq_all[wv], threadIdx.x % 64, wave, prog, consts, slots, a, b, c,
+                                 status, Bp, n_rows, row_begin, row_end);
 }
 
 __global__ void fill_one_row(Fr* row, size_t Bp) {
@@ -515,15 +588,30 @@ int solve_bi(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr* b, Fr* c, i
   return solve_rows(ctx, cs, slots, a, b, c, status, Bp, 0, cs->n_rows);
 }
 
-// one wavefront per 64 / S proofs; the instance with the big-integer division arm only for programs
-// that hold OP_EMUL units
+// one wavefront per 64 / S proofs, ctx->solve_waves of them per workgroup; the instance with the
+// big-integer division arm only for programs that hold OP_EMUL units
+// (the default is chosen by measurement, DESIGN §3.4: 1 / 2 / 4 / 8 gave 108.0 / 104.9 / 101.5 /
+// 109.5 ms per headline step)
+static constexpr unsigned SOLVE_WAVES_DEFAULT = 4;
 template <int S>
 static void launch_solve(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr* b, Fr* c,
                          int32_t* status, size_t Bp, uint32_t row_begin, uint32_t row_end) {
-  hipLaunchKernelGGL((cs->has_emul ? solve_vliw_kernel<S, true> : solve_vliw_kernel<S, false>),
-                     dim3((unsigned)(Bp * S / 64)), dim3(64), 0, ctx->stream,
+  // zkmi_set_solve_waves_per_block admits 0 (the default), 1, 2, 4 and 8
+  const unsigned wpb = ctx->solve_waves ? ctx->solve_waves : SOLVE_WAVES_DEFAULT;
+  const unsigned waves = (unsigned)(Bp * S / 64);
+  if (wpb == 1) {
+    hipLaunchKernelGGL((cs->has_emul ? solve_vliw_kernel<S, true> : solve_vliw_kernel<S, false>),
+                       dim3(waves), dim3(64), 0, ctx->stream, (const uint4*)cs->program, cs->consts,
+                       slots, a, b, c, status, Bp, cs->n_rows, row_begin, row_end);
+    return;
+  }
+  auto kernel = wpb > 4 ? (cs->has_emul ? solve_vliw_packed_kernel<S, true, 8>
+                                        : solve_vliw_packed_kernel<S, false, 8>)
+                        : (cs->has_emul ? solve_vliw_packed_kernel<S, true, 4>
+                                        : solve_vliw_packed_kernel<S, false, 4>);
+  hipLaunchKernelGGL(kernel, dim3((waves + wpb - 1) / wpb), dim3(64 * wpb), 0, ctx->stream,
                      (const uint4*)cs->program, cs->consts, slots, a, b, c, status, Bp, cs->n_rows,
-                     row_begin, row_end);
+                     row_begin, row_end, waves);
 }
 
 int solve_rows(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr* b, Fr* c, int32_t* status,

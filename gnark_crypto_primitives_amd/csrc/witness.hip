@@ -256,6 +256,14 @@ int zkmi_set_copy_threads(zkmi_ctx* ctx, int threads) {
   return ZKMI_OK;
 }
 
+int zkmi_set_solve_waves_per_block(zkmi_ctx* ctx, int waves) {
+  // 16 waves of 150 + 32 registers (184 allocated) cannot be resident on a CU's four SIMDs of 512
+  if (!ctx || (waves != 0 && waves != 1 && waves != 2 && waves != 4 && waves != 8))
+    return ZKMI_ERR_ARG;
+  ctx->solve_waves = waves;
+  return ZKMI_OK;
+}
+
 void zkmi_r1cs_free(zkmi_ctx* ctx, zkmi_r1cs* m) {
   if (!m) return;
   if (ctx) {

@@ -130,6 +130,7 @@ struct zkmi_ctx {
     unsigned next = 0;
   } ring;
   int copy_threads = 0;   // host threads that fill a pinned chunk from pageable memory; 0 = 4
+  int solve_waves = 0;    // wavefronts per workgroup of solve_vliw_kernel; 0 = the default (solve.hip)
 };
 
 // Window plan of a fixed-base table: W windows whose sizes sum to exactly 255 bits (scalars are

@@ -131,6 +131,7 @@ SYMBOLS = [
     ("zkmi_host_alloc", _P, [_P, _SZ]),
     ("zkmi_host_free", None, [_P, _P]),
     ("zkmi_set_copy_threads", _I, [_P, _I]),
+    ("zkmi_set_solve_waves_per_block", _I, [_P, _I]),
     ("zkmi_r1cs_load", _I, [_P, C.POINTER(R1csDesc), C.POINTER(_P)]),
     ("zkmi_r1cs_free", None, [_P, _P]),
     ("zkmi_prove_witness_submit", _I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _SZ, _P]),
@@ -486,6 +487,13 @@ class Context:
 
     def set_copy_threads(self, n):
         self._check(self.lib.zkmi_set_copy_threads(self.h, n), "zkmi_set_copy_threads")
+
+    def set_solve_waves_per_block(self, w):
+        """Wavefronts per workgroup of the solve kernel: 1, 2, 4 or 8; 0 restores the default."""
+        rc = self.lib.zkmi_set_solve_waves_per_block(self.h, w)
+        if rc != 0:
+            raise ZkmiError(f"zkmi_set_solve_waves_per_block({w}) refused ({rc}): "
+                            "0 (default), 1, 2, 4 or 8")
 
     def last_timings(self):
         arr = (C.c_double * 8)()

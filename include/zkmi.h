@@ -332,6 +332,10 @@ void* zkmi_host_alloc(zkmi_ctx* ctx, size_t bytes);
 void zkmi_host_free(zkmi_ctx* ctx, void* p);
 /* Host threads that copy pageable memory into the pinned ring (0 = default 4). */
 int zkmi_set_copy_threads(zkmi_ctx* ctx, int threads);
+/* Wavefronts per workgroup of the witness solve kernel: 1, 2, 4 or 8 (0 = default).  The solve of
+ * one batch runs beside the MSMs of another; packed into whole workgroups its wavefronts occupy
+ * fewer compute units.  Results do not depend on it.  Any other value is ZKMI_ERR_ARG. */
+int zkmi_set_solve_waves_per_block(zkmi_ctx* ctx, int waves);
 
 /* The R1CS matrices, so that a caller ships the wire vector only and a = L.w, b = R.w, c = O.w are
  * formed on the GPU ("zkmi_cs_load ... CSR A,B,C").  Mirrors gnark's
