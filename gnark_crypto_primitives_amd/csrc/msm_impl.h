@@ -7,6 +7,7 @@
 #include "zkmi_internal.h"
 #include "ec29.h"
 #include "comb_sign.h"
+#include "bit_transpose.h"
 #include "msm_part_layout.h"
 
 namespace zk {
@@ -598,6 +599,15 @@ static __global__ __launch_bounds__(1024) void comb_split_kernel(const uint8_t* 
   }
 }
 
+// A lane's 32-bit byte offset, opaque to the compiler at the place of use: an access at
+// scalar base + lane_offset_here(off) is selected as one global_load / global_store with the base
+// in scalar registers and the offset in one VGPR.  Without it the compiler widens the offset to 64
+// bits once, outside the loop, and every access adds base and offset in two vector registers.
+__device__ __forceinline__ uint32_t lane_offset_here(uint32_t off) {
+  asm volatile("" : "+v"(off));
+  return off;
+}
+
 // digits[j][p][b] = sum_i bit_j(s[gk+i][b]) << i for the varying group g = vlist[p].  SIGNED: k-bit
 // sign pattern M -> (index, negate): top bit set: entry M & (2^(k-1) - 1); clear: entry
 // ~M & (2^(k-1) - 1), negated (bit 31 of the digit).  SIGNED reads the table's native image t as
@@ -605,10 +615,18 @@ static __global__ __launch_bounds__(1024) void comb_split_kernel(const uint8_t* 
 // comb_sign_window names the window of every bit of t, the bits of window 253 are all ones, and
 // rows past n read as zero.  The row of a base at infinity is read like any other: its bits select
 // between entries that are equal (or both the identity), whatever they are.
-// A uniform group has lane 0's digits in every proof: only the
-// first wave of the blocks at x = 0 transposes it, and lane 0 writes d0[j][g] (comb_common_sums).
-// Three waves per SIMD (at most 168 VGPRs, which the 21 x 4 loaded words and the 32 transposed ones
-// leave room for): the pass waits on memory, and at two waves it measured 1.4 x slower.
+// A uniform group has lane 0's digits in every proof: only lane 0 of the grid transposes it and
+// writes d0[j][g] (comb_common_sums).
+// The transposes and the sign-pattern digit are bit_transpose.h's.  SIGNED feeds the group's top
+// row, k - 1, as row 31 (k is a run-time value, the slot is not), so that a pattern's top bit is
+// the sign bit of its window word; the rows below it keep their places 0 .. k - 2.
+// Addresses: window, group position and n_groups are wave-uniform, so every load and store is a
+// scalar base plus the lane's fixed 32-bit byte offset (b * 16 into a scalar row, b * 4 into a
+// window: Bp < 2^28 is the launch routine's check), and the window base advances by one scalar
+// stride per digit.  No vector address arithmetic is left in the loops.
+// At least three waves per SIMD (at most 168 VGPRs; the 21 x 4 loaded words and the 32 transposed
+// ones take 106 and leave room for four): the pass is bound by issue, and at two waves it measured
+// 1.4 x slower.  No scratch (profiles/r20_digits_kernel_resources.csv).
 template <int KMAX, bool SIGNED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void comb_digits_kernel(const Fr* __restrict__ sint,
                                                           const uint32_t* __restrict__ row_idx,
@@ -617,51 +635,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
                                                           const uint32_t* __restrict__ vpos,
                                                           uint32_t* __restrict__ digits,
                                                           uint32_t* __restrict__ d0) {
-  const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint4* base = reinterpret_cast<const uint4*>(sint);
+  constexpr int NLOW = SIGNED ? KMAX - 1 : KMAX;   // row slots below the top one
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t boff16 = b * 16u, boff4 = b * 4u;   // the lane's part of every address
+  const char* base = reinterpret_cast<const char*>(sint);
+  const size_t row_bytes = Bp * 16;                  // half a scalar row: four words per proof
   const uint32_t low = (1u << (k - 1)) - 1u;
   for (uint32_t g = blockIdx.y; g < n_groups; g += gridDim.y) {
     const uint32_t p = vpos[g];
     const bool uni = p == ~0u;
-    if (uni && (blockIdx.x != 0 || threadIdx.x >= 64)) continue;   // wave-uniform
-    if (SIGNED) {   // window 253: every sign is +, the entry of the all-ones pattern
-      if (!uni)
-        digits[((size_t)COMB_SIGN_ONES * n_groups + p) * Bp + b] = low;
-      else if (b == 0)
-        d0[(size_t)COMB_SIGN_ONES * n_groups + g] = low;
-    }
+    if (uni && b != 0) continue;
+    // window j of this group: wbase + j * wstride (+ boff4; lane 0 alone is here when uni)
+    char* const wbase = uni ? reinterpret_cast<char*>(d0 + g)
+                            : reinterpret_cast<char*>(digits + (size_t)p * Bp);
+    const size_t wstride = (uni ? (size_t)n_groups : (size_t)n_groups * Bp) * sizeof(uint32_t);
+    if (SIGNED)   // window 253: every sign is +, the entry of the all-ones pattern
+      *reinterpret_cast<uint32_t*>(wbase + (size_t)COMB_SIGN_ONES * wstride +
+                                   lane_offset_here(boff4)) = low;
+    // slot i < NLOW holds row i of the group, SIGNED: below the top row k - 1, which has the last
+    // slot; ~0: nothing to read (past k, or past n in a short last group)
     size_t rows[KMAX];   // wave-uniform
 #pragma unroll
     for (int i = 0; i < KMAX; i++) {
-      const size_t bi = (size_t)g * k + i;
-      rows[i] = (i < (int)k && bi < n) ? (row_idx ? (size_t)row_idx[bi] : bi) : ~(size_t)0;
+      const uint32_t r = SIGNED && i == NLOW ? k - 1 : (uint32_t)i;
+      const bool in_group = SIGNED ? (i == NLOW || (uint32_t)i + 1 < k) : (uint32_t)i < k;
+      const size_t bi = (size_t)g * k + r;
+      rows[i] = (in_group && bi < n) ? (row_idx ? (size_t)row_idx[bi] : bi) : ~(size_t)0;
     }
+    char* wnext = wbase;   // windows come in increasing order but for the parity window: jn is
+    int jn = 0;            // the window wnext stands at, a constant once the loops are unrolled
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       uint4 wv[KMAX];
 #pragma unroll
       for (int i = 0; i < KMAX; i++)
-        wv[i] = rows[i] != ~(size_t)0 ? base[(rows[i] * 2 + h) * Bp + b] : make_uint4(0, 0, 0, 0);
+        wv[i] = rows[i] != ~(size_t)0
+                    ? *reinterpret_cast<const uint4*>(base + (rows[i] * 2 + h) * row_bytes +
+                                                      lane_offset_here(boff16))
+                    : make_uint4(0, 0, 0, 0);
 #pragma unroll
       for (int c = 0; c < 4; c++) {
-        // 32 x 32 bit transpose (rows = bases of the group, columns = 32 scalar bits): afterwards
-        // m[bit] holds, in bit i, bit `bit` of base i's word -- the window's index.  Five
-        // butterfly stages of 16 masked swaps instead of 32 x k single-bit extractions.
         uint32_t m[32];
 #pragma unroll
-        for (int i = 0; i < 32; i++)
-          m[i] = i < KMAX ? (c == 0 ? wv[i].x : c == 1 ? wv[i].y : c == 2 ? wv[i].z : wv[i].w) : 0u;
-#pragma unroll
-        for (int jj = 16; jj != 0; jj >>= 1) {
-          const uint32_t mask = jj == 16 ? 0x0000ffffu : jj == 8 ? 0x00ff00ffu : jj == 4 ? 0x0f0f0f0fu
-                                : jj == 2 ? 0x33333333u : 0x55555555u;
-#pragma unroll
-          for (int kk = 0; kk < 32; kk = (kk + jj + 1) & ~jj) {
-            const uint32_t t = ((m[kk] >> jj) ^ m[kk + jj]) & mask;
-            m[kk] ^= t << jj;
-            m[kk + jj] ^= t;
-          }
+        for (int i = 0; i < 32; i++) {
+          const int s = i < NLOW ? i : (SIGNED && i == 31) ? NLOW : -1;
+          m[i] = s < 0 ? 0u : c == 0 ? wv[s].x : c == 1 ? wv[s].y : c == 2 ? wv[s].z : wv[s].w;
         }
+        bit_transpose32<NLOW, SIGNED>(m);
+        const uint32_t woff = lane_offset_here(boff4);
 #pragma unroll
         for (int bit = 0; bit < 32; bit++) {
           int j = (h * 4 + c) * 32 + bit;
@@ -672,12 +693,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
           } else if (j >= COMB_W) {
             break;
           }
-          uint32_t idx = comp ? ~m[bit] : m[bit];
-          if (SIGNED) idx = ((idx >> (k - 1)) & 1u) ? (idx & low) : ((~idx & low) | 0x80000000u);
-          if (!uni)
-            digits[((size_t)j * n_groups + p) * Bp + b] = idx;
-          else if (b == 0)
-            d0[(size_t)j * n_groups + g] = idx;
+          const uint32_t x = comp ? ~m[bit] : m[bit];
+          char* dst = wbase + (size_t)j * wstride;
+          if (j == jn) {
+            dst = wnext;
+            wnext += wstride;
+            jn++;
+          }
+          *reinterpret_cast<uint32_t*>(dst + woff) = SIGNED ? comb_sign_digit(x, low) : x;
         }
       }
     }
@@ -1123,6 +1146,7 @@ int run_comb(zkmi_ctx* ctx, const zkmi_msm_bases* bases, const Fr* scalars, cons
   const bool sg = bases->plan.comb_signed != 0;
   const size_t G = bases->n_groups;
   const int W = bases->plan.W;   // 254, + the correction window of signed tables
+  if (Bp >> 28) return ZKMI_ERR_ARG;   // comb_digits_kernel: a lane's byte offsets are 32-bit
   // measured at 4 / 8 / 12 / 16 / 24: 277 / 275 / 273.5 / 272 / 273.6 ms per Arbo-160 batch
   const size_t comb_factor = bases->chunk_factor ? bases->chunk_factor : 16;
   const ChunkSplit cs = split_chunks(G, comb_factor * 262144 / Bp / (size_t)W);
