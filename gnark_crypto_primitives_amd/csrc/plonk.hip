@@ -50,6 +50,7 @@ struct zkmi_plonk_pk {
   struct Commit {
     uint32_t n_rows = 0, row = 0;
     std::vector<uint32_t> slots;        // host: value-file slots of the operands (may be empty)
+    std::vector<uint32_t> rows;         // host: C_i (the solver entry compares its hints' wires with them)
     uint32_t* rows_dev = nullptr;       // n_rows + 2: C_i, then the blinding rows r_i and n - 1
     uint32_t* slots_dev = nullptr;      // n_rows, or null
     zkmi_msm_bases* lag = nullptr;      // subset-sum tables of the n_rows + 2 Lagrange points
@@ -1784,6 +1785,28 @@ static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
     scs->checked_key = pk->serial;
   }
   const size_t n_c = pk->commits.size();
+  // a solver behind a key with commitments (zkmi_plonk_prove_scs_ex): its commitment hints are the
+  // key's commitments, one by one
+  if (solver && (n_c || scs_solver_commits(solver))) {
+    if (scs_solver_commits(solver) != n_c) {
+      ctx->err = "plonk solver: the key carries " + std::to_string(n_c) + " commitments, the solver's plan holds " +
+                 std::to_string(scs_solver_commits(solver)) + " commitment hints";
+      return ZKMI_ERR_ARG;
+    }
+    for (size_t i = 0; i < n_c; i++) {
+      const ScsSolverCommit h = scs_solver_commit(solver, i);
+      const zkmi_plonk_pk::Commit& c = pk->commits[i];
+      bool same = h.n_wires == c.n_rows && c.row < scs->n_gates && h.wire == scs->hx[0][c.row];
+      for (uint32_t j = 0; same && j < c.n_rows; j++)
+        same = c.rows[j] < scs->n_gates && h.wires[j] == scs->hx[0][c.rows[j]];
+      if (!same) {
+        ctx->err = "plonk solver: commitment hint " + std::to_string(i) + " of the plan is not commitment " +
+                   std::to_string(i) + " of the key: its committed wires must be xa[rows[j]] in order and its "
+                   "output xa[row]";
+        return ZKMI_ERR_ARG;
+      }
+    }
+  }
   if ((rc = round1_begin(ctx, pk, batch))) return rc;
   const size_t Bp = pk->Bp;
   if (n_c && (rc = commit_begin(ctx, pk, blind_commit, batch, Bp))) return rc;
@@ -1798,8 +1821,25 @@ static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
   rc = transpose_in(ctx, tbl.p, pk->small[0].p, 9, batch, Bp, 32);
   if (!rc && scs) {
     // the solver stages its inputs through A, which the gather below overwrites
-    rc = solver ? scs_solver_run(ctx, solver, wires, batch, Bp, A, W, (int32_t*)st)
-                : stage_rows(ctx, wires, scs->n_wires, batch, Bp, W);
+    if (solver && n_c) {
+      // per commitment: the steps up to its boundary, the commitment step on the committed wires
+      // straight from the wire matrix (gnark's image), H_i into the commitment wire's row
+      rc = scs_solver_stage(ctx, solver, wires, batch, Bp, A, W);
+      uint32_t at = 0;
+      for (size_t i = 0; !rc && i < n_c; i++) {
+        const ScsSolverCommit h = scs_solver_commit(solver, i);
+        rc = scs_solver_run_steps(ctx, solver, W, (int32_t*)st, Bp, at, h.step);
+        at = h.step;
+        if (!rc) rc = commit_from_rows(ctx, pk, (uint32_t)i, W, h.wires_dev, false, Bp, batch);
+        if (!rc && hipMemcpyAsync(W + (size_t)h.wire * Bp, (const Fr*)pk->cm_h.p + i * Bp, Bp * sizeof(Fr),
+                                  hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+          rc = ZKMI_ERR_HIP;
+      }
+      if (!rc) rc = scs_solver_run_steps(ctx, solver, W, (int32_t*)st, Bp, at, scs_solver_steps(solver));
+    } else {
+      rc = solver ? scs_solver_run(ctx, solver, wires, batch, Bp, A, W, (int32_t*)st)
+                  : stage_rows(ctx, wires, scs->n_wires, batch, Bp, W);
+    }
     if (!rc) {
       const ScsDev dev{{scs->x[0], scs->x[1], scs->x[2]}, scs->marks, scs->sel, scs->n_gates,
                        scs->n_public, pk->cm_skip};
@@ -1822,7 +1862,8 @@ static int round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs* scs,
     if (n_gates < n)
       hipLaunchKernelGGL(plonk_zero_rows, dim3((unsigned)(Bp / 64), 64), dim3(64), 0, ctx->stream, A,
                          n_gates, n, Bp);
-    for (size_t i = 0; !rc && i < n_c; i++)
+    // (behind the solver the step has run already, on the same values: cm_pts / cm_H / cm_h hold it)
+    for (size_t i = 0; !rc && !solver && i < n_c; i++)
       rc = commit_from_rows(ctx, pk, (uint32_t)i, A, pk->commits[i].rows_dev, false, Bp, batch);
     if (!rc) {
       hipLaunchKernelGGL(plonk_commit_check, dim3((unsigned)(Bp / 64)), dim3(64), 0, ctx->stream,
@@ -1895,6 +1936,9 @@ static int prove_after_round1_witness(zkmi_ctx* ctx, zkmi_plonk_pk* pk, size_t b
 static const char* const kNoCommitmentsScs =
     "plonk: this key carries commitments: the solver entries (zkmi_plonk_round1_scs / "
     "zkmi_plonk_prove_scs) do not carry them; solve with gnark and use zkmi_plonk_prove_witness_ex";
+static const char* const kCommitHintsScs =
+    "scs solver: the plan holds commitment hints: their values need a proving key; use "
+    "zkmi_plonk_prove_scs_ex with the key that carries the commitments";
 int zkmi_scs_solve_batch(zkmi_ctx* ctx, const zkmi_scs_solver* solver, const void* inputs, size_t batch,
                          void* wires_out, int32_t* status_out) {
   if (!ctx) return ZKMI_ERR_ARG;
@@ -1904,6 +1948,10 @@ int zkmi_scs_solve_batch(zkmi_ctx* ctx, const zkmi_scs_solver* solver, const voi
   if (batch == 0) return ZKMI_OK;
   if (!solver || !status_out || (scs_solver_inputs(solver) && !inputs)) {
     ctx->err = "scs_solve_batch: null argument";
+    return ZKMI_ERR_ARG;
+  }
+  if (scs_solver_commits(solver)) {
+    ctx->err = kCommitHintsScs;
     return ZKMI_ERR_ARG;
   }
   const zkmi_scs* scs = scs_solver_system(solver);
@@ -1942,6 +1990,10 @@ int zkmi_plonk_round1_scs(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solve
     ctx->err = kNoCommitmentsScs;
     return ZKMI_ERR_ARG;
   }
+  if (scs_solver_commits(solver)) {
+    ctx->err = kCommitHintsScs;
+    return ZKMI_ERR_ARG;
+  }
   return round1_witness(ctx, pk, scs_solver_system(solver), inputs, nullptr, nullptr, nullptr, 0, batch, blind,
                         nullptr, commits_out, status_out, solver);
 }
@@ -1957,6 +2009,23 @@ int zkmi_plonk_prove_scs(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver
   int rc = zkmi_plonk_round1_scs(ctx, pk, solver, inputs, batch, blind, abc.data(), status_out);
   if (rc) return rc;
   return prove_after_round1_witness(ctx, pk, batch, abc, vk_digest, proofs_out, nullptr);
+}
+int zkmi_plonk_prove_scs_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver* solver,
+                            const void* inputs, size_t batch, const void* blind, const void* blind_commit,
+                            const uint8_t* vk_digest, void* proofs_out, void* commit_out,
+                            int32_t* status_out) {
+  if (!ctx) return ZKMI_ERR_ARG;
+  if (!pk || !solver || !blind || !vk_digest || !proofs_out || !status_out || batch == 0 ||
+      (scs_solver_inputs(solver) && !inputs)) {
+    ctx->err = "plonk_prove_scs: null argument or empty batch";
+    return ZKMI_ERR_ARG;
+  }
+  if (int bad = commit_args_check(ctx, pk, blind_commit, commit_out)) return bad;
+  std::vector<G1Affine> abc(batch * 3);
+  int rc = round1_witness(ctx, pk, scs_solver_system(solver), inputs, nullptr, nullptr, nullptr, 0, batch, blind,
+                          blind_commit, abc.data(), status_out, solver);
+  if (rc) return rc;
+  return prove_after_round1_witness(ctx, pk, batch, abc, vk_digest, proofs_out, commit_out);
 }
 
 // ---- commitments of a key (api.Commit under PLONK; parity with gnark unpinned) ----------------------
@@ -2019,6 +2088,7 @@ int zkmi_plonk_pk_set_commitments(zkmi_ctx* ctx, zkmi_plonk_pk* pk,
     zkmi_plonk_pk::Commit& c = cm[i];
     c.n_rows = d.n_rows;
     c.row = d.row;
+    c.rows = rows[i];
     std::vector<uint32_t> all(rows[i]);
     all.push_back(d.row);
     all.push_back((uint32_t)(n - 1));

@@ -45,6 +45,26 @@
 //           (the loader lifts the first four to 2^261 images for the 29-bit products);
 //           K: LIN -1 / k, DIV k
 //     aux   NBITS: j0 | count << 16
+//     word 3  0 for the four classes above; otherwise a class of ZKMI_HINTS_STD, which then stands
+//             in place of bits 16 .. 17 (those read 0):
+//       SK_LIMBS       like NBITS; aux = j0 | count << 16 | width << 24: wire outs[target + i] = bits
+//                      [(j0 + i) width, (j0 + i + 1) width) of the canonical value of v
+//       SK_BYTEOP      the two terms sit on positions a and b (a constant term: qC for a, K for b,
+//                      both in gnark's image, marked like qC); aux = 1 XOR | 2 AND on the low 32 bits
+//       SK_COUNT_ZERO  zeroes the rows of wires outs[target .. target + count), aux = count << 16:
+//                      their low words are the counters of the lookup
+//       SK_COUNT_Q     one query v: adds 1 to the counter of wire outs[target + v] when v < aux, the
+//                      table's size (an atomic: queries of one step may meet on a counter)
+//       SK_COUNT_END   reads the counters of outs[target .. target + count) back and stores their
+//                      field images in place
+//     The three COUNT classes are three levels: ZERO at level 1, a query at least one level above
+//     ZERO and above its producer, END above every query; the output wires carry END's level.
+// A commitment hint (ZKMI_HINT_COMMIT) has no record: the kernel never runs it.  Its wire's level is
+// one above the highest level of its committed wires (and no lower than the level of the commitment
+// before it), and that level is a barrier: ScsPlan::commits lists, per hint, the first step of the
+// barrier level.  Every record at a lower level lies before that step, every record that reads the
+// commitment wire behind it; the caller runs the steps up to it, forms the commitment, stores the
+// challenge in the wire's row and goes on.
 // The records end with S records of padding: the kernel fetches one step ahead.
 //
 // Every count the kernel loops over and every index it uses as an address comes out of
@@ -64,7 +84,9 @@
 
 namespace zk {
 
-enum { SK_LIN = 0, SK_DIV = 1, SK_INVZERO = 2, SK_NBITS = 3 };
+enum { SK_LIN = 0, SK_DIV = 1, SK_INVZERO = 2, SK_NBITS = 3,
+       // ZKMI_HINTS_STD: in word 3 of quad 1
+       SK_LIMBS = 4, SK_BYTEOP = 5, SK_COUNT_ZERO = 6, SK_COUNT_Q = 7, SK_COUNT_END = 8 };
 constexpr uint32_t SCS_NONE = 0xffffffffu;      // input_wire: no gate reads it; hint_in_wire: a constant
 constexpr uint32_t SCS_NBITS_CHUNK = 16;        // bits per NBITS record
 enum {
@@ -76,8 +98,10 @@ constexpr int SCS_COEF_ROW = 6;                 // field elements per row of the
 
 struct ScsRecord {
   uint32_t wa, wb, wc, target;
-  uint32_t ctl, coef, aux, zero;
+  uint32_t ctl, coef, aux, xcls;
 };
+// the class of a record: word 3 where it is set, else bits 16 .. 17 of ctl
+inline uint32_t scs_record_class(const ScsRecord& r) { return r.xcls ? r.xcls : (r.ctl >> SCS_CTL_CLASS) & 3; }
 
 struct ScsPlanIn {
   uint32_t n_wires = 0, n_gates = 0, n_public = 0;
@@ -91,6 +115,13 @@ struct ScsPlan {
   std::vector<Fr> coefs;            // rows of SCS_COEF_ROW; row 0 is all zero
   std::vector<uint32_t> outs;       // output wires of the NBITS records
   std::vector<uint32_t> input_wire; // n_inputs
+  // ZKMI_HINTS_STD
+  bool std_records = false;         // a record of a class from SK_LIMBS on: scs_std_kernel runs the plan
+  struct Commit {
+    uint32_t instr, step, wire;     // the hint's instruction, the first step of its barrier level, its wire
+    std::vector<uint32_t> wires;    // the committed wires, operand order
+  };
+  std::vector<Commit> commits;      // commitment i at [i]; steps do not decrease
 };
 
 // S for lanes_per_proof = 0: the power of two in 1 .. 16 nearest to the mean number of records per
@@ -99,8 +130,9 @@ inline uint32_t scs_auto_lanes(uint64_t n_records, uint32_t n_levels) {
   return r1cs_auto_lanes(n_records, n_levels);
 }
 
-// Returns the empty string and the plan, or what is wrong with the description.
-inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out) {
+// Returns the empty string and the plan, or what is wrong with the description.  max_set: the highest
+// hint set the caller can run (zkmi_scs_solver_load: ZKMI_HINTS_STD).
+inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out, uint32_t max_set = ZKMI_HINTS_BASIC) {
   const std::string pre = "scs solver: ";
   if (!in.desc || !in.x[0] || !in.x[1] || !in.x[2] || !in.sel) return pre + "null argument";
   const zkmi_scs_solver_desc& d = *in.desc;
@@ -108,8 +140,12 @@ inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out) {
     return pre + "the system needs 1 .. 2^32 - 2 wires and 1 .. 2^24 gates";
   uint32_t S = d.lanes_per_proof;
   if (S > 64 || (S & (S - 1))) return pre + "lanes_per_proof must be 0 (auto) or a power of two, 1 .. 64";
-  if (d.hint_set != ZKMI_HINTS_BASIC)
-    return pre + "hint_set must be ZKMI_HINTS_BASIC (0): this entry solves InvZero and NBits hints only";
+  if (d.hint_set != ZKMI_HINTS_BASIC && (max_set == ZKMI_HINTS_BASIC || d.hint_set != ZKMI_HINTS_STD))
+    return pre + (max_set == ZKMI_HINTS_BASIC
+                      ? "hint_set must be ZKMI_HINTS_BASIC (0): this entry solves InvZero and NBits hints only"
+                      : "hint_set must be ZKMI_HINTS_BASIC (0) or ZKMI_HINTS_STD (1): this entry has no "
+                        "other set (the emulated product, kind 7, is not solved here)");
+  const bool std_set = d.hint_set == ZKMI_HINTS_STD;
   if (d.n_inputs < in.n_public || in.n_public > in.n_gates)
     return pre + "n_inputs = " + std::to_string(d.n_inputs) + " is inconsistent with the system's n_public = " +
            std::to_string(in.n_public) + " (the public inputs come first)";
@@ -157,6 +193,8 @@ inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out) {
   };
   std::vector<Pending> pend;
   std::vector<uint32_t> houts;
+  std::vector<uint32_t> xouts;          // the outputs of the std hints: they follow the NBITS records' in outs
+  std::vector<ScsPlan::Commit> commits; // .step: the barrier level until the records are packed
   uint32_t n_levels = 0;
   const Fr* hcoef = (const Fr*)d.hint_in_coef;
   const size_t ng = in.n_gates;
@@ -177,13 +215,142 @@ inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out) {
       if (idx >= d.n_hints) return at + ": hint index " + std::to_string(idx) + " out of range";
       const uint32_t hk = d.hint_kind[idx];
       const std::string hat = at + " (hint " + std::to_string(idx) + ")";
-      if (hk >= ZKMI_HINT_LIMBS && hk <= ZKMI_HINT_EMULMUL)
+      if (hk >= ZKMI_HINT_LIMBS && hk <= ZKMI_HINT_EMULMUL && (!std_set || hk == ZKMI_HINT_EMULMUL))
         return hat + ": hints " + r1cs_hint_name(hk) + " are not supported on this entry";
-      if (hk != ZKMI_HINT_INVZERO && hk != ZKMI_HINT_NBITS)
+      if (hk == 0 || hk > ZKMI_HINT_EMULMUL)
         return hat + ": hints " + r1cs_hint_name(hk) + " (" + std::to_string(hk) + ") are not supported on this entry";
       const uint32_t in0 = d.hint_in_ptr[idx], nin = d.hint_in_ptr[idx + 1] - in0;
       const uint32_t o0 = d.hint_out_ptr[idx], nout = d.hint_out_ptr[idx + 1] - o0;
       const std::string name = r1cs_hint_name(hk);
+      if (hk >= ZKMI_HINT_LIMBS) {
+        // ---- ZKMI_HINTS_STD: p0, a constant, then the operands --------------------------------------
+        if (nin == 0) return hat + ": " + name + " takes a parameter p0 as its first input";
+        if (d.hint_in_wire[in0] != SCS_NONE)
+          return hat + ": " + name + ": the parameter p0 reads wire " + std::to_string(d.hint_in_wire[in0]) +
+                 "; it must be a constant";
+        for (uint32_t t = in0; t < in0 + nin; t++) {
+          if (!fr_is_reduced(hcoef[t])) return hat + ": the coefficient of input " + std::to_string(t - in0) + " is not reduced mod r";
+          const uint32_t w = d.hint_in_wire[t];
+          if (w == SCS_NONE) continue;
+          if (w >= in.n_wires) return hat + ": input wire " + std::to_string(w) + " out of range";
+          if (!solved[w]) return hat + ": reads wire " + std::to_string(w) + ", which is not solved yet";
+        }
+        const Fr p0f = from_mont(hcoef[in0]);
+        const bool p0_small = !(p0f.v[1] | p0f.v[2] | p0f.v[3] | p0f.v[4] | p0f.v[5] | p0f.v[6] | p0f.v[7]);
+        const uint32_t p0 = p0_small ? p0f.v[0] : 0xffffffffu;
+        for (uint32_t o = o0; o < o0 + nout; o++) {
+          const uint32_t wire = d.hint_out[o];
+          if (wire >= in.n_wires) return hat + ": output wire " + std::to_string(wire) + " out of range";
+          if (solved[wire]) return hat + ": output wire " + std::to_string(wire) + " is already solved";
+          solved[wire] = 1;   // (a wire twice among the outputs is "already solved" at its second entry)
+        }
+        // term t of the hint on position col: coef * wire through the selector, a constant through
+        // qC (col 0) or K (col 1)
+        auto term = [&](uint32_t t, int col) {
+          const uint32_t w = d.hint_in_wire[t];
+          const Fr k = hcoef[t];
+          if (w == SCS_NONE) {
+            const int q = col == 0 ? 4 : 5;
+            p.coef[q] = k;
+            const uint32_t m = scs_mark(k) == SCS_MARK_ZERO ? SCS_MARK_ZERO : SCS_MARK_GENERAL;
+            if (q == 4) set_mark(4, m);
+            else p.r.ctl = (p.r.ctl & ~(3u << SCS_CTL_MARK_K)) | m << SCS_CTL_MARK_K;
+          } else {
+            p.coef[col] = k;
+            set_mark(col, scs_mark(k));
+            if (scs_mark(k) != SCS_MARK_ZERO) reads(col, w);
+            else lv = std::max(lv, level[w]);
+          }
+        };
+        auto set_levels = [&](uint32_t l) {
+          for (uint32_t o = o0; o < o0 + nout; o++) level[d.hint_out[o]] = l;
+          n_levels = std::max(n_levels, l);
+        };
+        // the outputs [j0, j0 + cnt) of the hint as one record of class cls; `first` = the hint's
+        // first entry in xouts
+        auto chunks = [&](uint32_t cls, uint32_t first, uint32_t aux_hi) {
+          p.cls = cls;
+          for (uint32_t j0 = 0; j0 < nout; j0 += SCS_NBITS_CHUNK) {
+            const uint32_t cnt = std::min(SCS_NBITS_CHUNK, nout - j0);
+            p.first_out = first + j0;
+            p.r.aux = (cls == SK_LIMBS ? j0 : 0) | cnt << 16 | aux_hi;
+            pend.push_back(p);
+          }
+        };
+        if (hk == ZKMI_HINT_LIMBS) {
+          if (nin != 2 || nout == 0) return hat + ": " + name + " takes p0 = the width and one value, and has outputs";
+          if (p0 < 1 || p0 > 64) return hat + ": " + name + ": the width p0 must be in 1 .. 64";
+          if (nout > 0xffffu) return hat + ": " + name + " with more than 65535 outputs";
+          term(in0 + 1, 0);
+          const uint32_t first = (uint32_t)xouts.size();
+          xouts.insert(xouts.end(), d.hint_out + o0, d.hint_out + o0 + nout);
+          p.level = lv + 1;
+          p.r.ctl |= SCS_CTL_STORE;
+          chunks(SK_LIMBS, first, p0 << 24);
+          set_levels(lv + 1);
+        } else if (hk == ZKMI_HINT_BYTEOP) {
+          if (nin != 3 || nout != 1) return hat + ": " + name + " takes p0 = the operation and two values, and has one output";
+          if (p0 != 1 && p0 != 2) return hat + ": " + name + ": the operation p0 must be 1 (XOR) or 2 (AND)";
+          term(in0 + 1, 0);
+          term(in0 + 2, 1);
+          p.cls = SK_BYTEOP;
+          p.level = lv + 1;
+          p.r.ctl |= SCS_CTL_STORE;
+          p.r.target = d.hint_out[o0];
+          p.r.aux = p0;
+          pend.push_back(p);
+          set_levels(lv + 1);
+        } else if (hk == ZKMI_HINT_COUNT) {
+          if (nout == 0 || p0 != nout)
+            return hat + ": " + name + ": the table size p0 must be the number of outputs, " + std::to_string(nout);
+          const uint32_t first = (uint32_t)xouts.size();
+          xouts.insert(xouts.end(), d.hint_out + o0, d.hint_out + o0 + nout);
+          const Pending blank = p;
+          p.level = 1;
+          p.r.ctl |= SCS_CTL_STORE;
+          chunks(SK_COUNT_ZERO, first, 0);
+          uint32_t top = 1;
+          for (uint32_t t = in0 + 1; t < in0 + nin; t++) {
+            p = blank;
+            lv = 0;
+            term(t, 0);
+            p.cls = SK_COUNT_Q;
+            p.level = std::max(lv + 1, 2u);
+            p.r.ctl |= SCS_CTL_STORE;
+            p.first_out = first;
+            p.r.aux = nout;
+            pend.push_back(p);
+            top = std::max(top, p.level);
+          }
+          p = blank;
+          p.level = top + 1;
+          p.r.ctl |= SCS_CTL_STORE;
+          chunks(SK_COUNT_END, first, 0);
+          set_levels(top + 1);
+        } else {   // ZKMI_HINT_COMMIT
+          if (nin < 2 || nout != 1) return hat + ": " + name + " takes p0 = its index and the committed wires, and has one output";
+          if (p0 != commits.size())
+            return hat + ": " + name + ": the index p0 must count the commitment hints in instruction order, here " +
+                   std::to_string(commits.size());
+          if (commits.size() >= ZKMI_PLONK_MAX_COMMITMENTS)
+            return hat + ": " + name + ": more than " + std::to_string(ZKMI_PLONK_MAX_COMMITMENTS) + " commitments";
+          ScsPlan::Commit c;
+          c.instr = ii;
+          c.wire = d.hint_out[o0];
+          uint32_t l = commits.empty() ? 0 : level[commits.back().wire] - 1;
+          for (uint32_t t = in0 + 1; t < in0 + nin; t++) {
+            const uint32_t w = d.hint_in_wire[t];
+            if (w == SCS_NONE || !(hcoef[t] == Fr::one()))
+              return hat + ": " + name + ": operand " + std::to_string(t - in0 - 1) + " must be a wire with coefficient 1";
+            c.wires.push_back(w);
+            l = std::max(l, level[w]);
+          }
+          c.step = l + 1;   // the barrier level; its first step once the records are packed
+          commits.push_back(c);
+          set_levels(l + 1);
+        }
+        continue;
+      }
       if (nin != 1 || nout == 0 || (hk == ZKMI_HINT_INVZERO && nout != 1))
         return hat + ": " + name + " takes one input" +
                (hk == ZKMI_HINT_INVZERO ? " and has one output" : " and has outputs");
@@ -321,13 +488,19 @@ inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out) {
   }
   auto pad_to_step = [&](uint32_t cls) {
     while (P.records.size() % S)
-      P.records.push_back(ScsRecord{0, 0, 0, 0, SCS_CTL_NO_TERMS |
-                                                    cls << SCS_CTL_CLASS, 0, 0, 0});
+      P.records.push_back(ScsRecord{0, 0, 0, 0, SCS_CTL_NO_TERMS | (cls < SK_LIMBS ? cls : 0) << SCS_CTL_CLASS,
+                                    0, 0, cls < SK_LIMBS ? 0 : cls});
   };
+  uint32_t nbits_outs = 0;
+  for (const Pending& p : pend)
+    if (p.cls == SK_NBITS) nbits_outs += p.n_out;
+  std::vector<std::pair<uint32_t, uint32_t>> level_step;   // (level, its first step), increasing
   for (size_t i = 0; i < order.size(); i++) {
     Pending& p = pend[order[i]];
     if (i && (pend[order[i - 1]].level != p.level || pend[order[i - 1]].cls != p.cls))
       pad_to_step(pend[order[i - 1]].cls);
+    if (level_step.empty() || level_step.back().first != p.level)
+      level_step.emplace_back(p.level, (uint32_t)(P.records.size() / S));
     if ((uint64_t)P.records.size() + 2 * S > 0xffffffffull) return pre + "more than 2^32 plan records";
     std::array<uint32_t, 8 * SCS_COEF_ROW> key;
     for (int s = 0; s < SCS_COEF_ROW; s++)
@@ -338,7 +511,13 @@ inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out) {
       P.coefs.insert(P.coefs.end(), p.coef, p.coef + SCS_COEF_ROW);
     }
     p.r.coef = it->second;
-    p.r.ctl |= p.cls << SCS_CTL_CLASS;
+    if (p.cls < SK_LIMBS) {
+      p.r.ctl |= p.cls << SCS_CTL_CLASS;
+    } else {
+      p.r.xcls = p.cls;
+      P.std_records = true;
+      if (p.cls != SK_BYTEOP) p.r.target = nbits_outs + p.first_out;
+    }
     if (p.cls == SK_NBITS) {
       p.r.target = (uint32_t)P.outs.size();
       P.outs.insert(P.outs.end(), houts.begin() + p.first_out, houts.begin() + p.first_out + p.n_out);
@@ -350,23 +529,36 @@ inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out) {
   P.n_steps = (uint32_t)(P.records.size() / S);
   for (uint32_t s = 0; s < S; s++)
     P.records.push_back(ScsRecord{0, 0, 0, 0, SCS_CTL_NO_TERMS, 0, 0, 0});
+  P.outs.insert(P.outs.end(), xouts.begin(), xouts.end());
+  for (ScsPlan::Commit& c : commits) {
+    const uint32_t barrier = c.step;
+    c.step = P.n_steps;
+    for (const auto& ls : level_step)
+      if (ls.first >= barrier) {
+        c.step = ls.second;
+        break;
+      }
+  }
+  P.commits = std::move(commits);
   return "";
 }
 
-// What a record computes, on the host (the device's twin is scs_solve_kernel): `ld(w)` reads a wire,
-// `st(w, v)` stores one; returns false when the record divides by zero.  coefs: the plan's table in
-// gnark's image.
+// What a record computes, on the host (the device's twins are scs_solve_kernel and scs_std_kernel):
+// `ld(w)` reads a wire, `st(w, v)` stores one; returns false when the record divides by zero.  coefs:
+// the plan's table in gnark's image.  A lookup counter is the low word of its wire's row, as on the
+// device: COUNT_Q reads the row and stores it back with that word one higher.
 template <class Load, class Store>
 inline bool scs_record_run(const ScsRecord& r, const Fr* coefs, const uint32_t* outs, Load ld, Store st) {
   const Fr* q = coefs + (size_t)r.coef * SCS_COEF_ROW;
-  const uint32_t cls = (r.ctl >> SCS_CTL_CLASS) & 3;
+  const uint32_t cls = scs_record_class(r);
   auto term = [&](uint32_t mark, const Fr& x, const Fr& k) {
     return mark == SCS_MARK_ZERO ? Fr::zero() : mark == SCS_MARK_ONE ? x : mark == SCS_MARK_MINUS_ONE ? neg(x) : mul(x, k);
   };
   const Fr zero = Fr::zero();
   const Fr va = r.ctl >> SCS_CTL_READ & 1 ? ld(r.wa) : zero, vb = r.ctl >> (SCS_CTL_READ + 1) & 1 ? ld(r.wb) : zero,
            vc = r.ctl >> (SCS_CTL_READ + 2) & 1 ? ld(r.wc) : zero;
-  Fr rest = add(add(term(r.ctl & 3, va, q[0]), term((r.ctl >> 2) & 3, vb, q[1])), term((r.ctl >> 4) & 3, vc, q[2]));
+  const Fr ta = term(r.ctl & 3, va, q[0]), tb = term((r.ctl >> 2) & 3, vb, q[1]);
+  Fr rest = add(add(ta, tb), term((r.ctl >> 4) & 3, vc, q[2]));
   if (((r.ctl >> 8) & 3) != SCS_MARK_ZERO) rest = add(rest, q[4]);
   const uint32_t mm = (r.ctl >> 6) & 3, mk = (r.ctl >> SCS_CTL_MARK_K) & 3;
   const bool store = r.ctl & SCS_CTL_STORE;
@@ -382,6 +574,27 @@ inline bool scs_record_run(const ScsRecord& r, const Fr* coefs, const uint32_t* 
     }
   } else if (cls == SK_INVZERO) {
     if (store) st(r.target, inverse(rest));
+  } else if (cls == SK_LIMBS) {
+    const Fr v = from_mont(rest);
+    const uint32_t j0 = r.aux & 0xffffu, cnt = (r.aux >> 16) & 0xffu, width = r.aux >> 24;
+    for (uint32_t j = 0; store && j < cnt; j++)
+      st(outs[r.target + j], r1cs_small(r1cs_limb(v, (j0 + j) * width, width)));
+  } else if (cls == SK_BYTEOP) {
+    const Fr a = ((r.ctl >> 8) & 3) != SCS_MARK_ZERO ? add(ta, q[4]) : ta, b = mk != SCS_MARK_ZERO ? add(tb, q[5]) : tb;
+    const uint32_t u = from_mont(a).v[0], v = from_mont(b).v[0];
+    if (store) st(r.target, r1cs_small(r.aux == 1 ? u ^ v : u & v));
+  } else if (cls == SK_COUNT_ZERO) {
+    for (uint32_t j = 0; store && j < r.aux >> 16; j++) st(outs[r.target + j], zero);
+  } else if (cls == SK_COUNT_Q) {
+    const Fr v = from_mont(rest);
+    if (store && (v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0 && v.v[0] < r.aux) {
+      Fr c = ld(outs[r.target + v.v[0]]);
+      c.v[0]++;
+      st(outs[r.target + v.v[0]], c);
+    }
+  } else if (cls == SK_COUNT_END) {
+    for (uint32_t j = 0; store && j < r.aux >> 16; j++)
+      st(outs[r.target + j], r1cs_small(ld(outs[r.target + j]).v[0]));
   } else {
     const Fr v = from_mont(rest);
     const uint32_t j0 = r.aux & 0xffffu, cnt = r.aux >> 16;

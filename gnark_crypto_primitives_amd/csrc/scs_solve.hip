@@ -34,6 +34,11 @@ struct zkmi_scs_solver {
   Fr* coefs = nullptr;       // rows of six: qL qR qO qM as 2^261 images, qC and K in gnark's image
   uint32_t* outs = nullptr;
   uint32_t* input_wire = nullptr;
+  // ZKMI_HINTS_STD: a plan with records of the std classes runs scs_std_kernel (scs_solve_std.hip);
+  // the commitment hints, with the solver's device copy of their wire lists
+  bool std_records = false;
+  std::vector<ScsPlan::Commit> commits;
+  std::vector<uint32_t*> commit_wires;
 };
 
 namespace zk {
@@ -155,15 +160,41 @@ static void launch_scs_solve(zkmi_ctx* ctx, const zkmi_scs_solver* s, Fr* w, int
 
 const zkmi_scs* scs_solver_system(const zkmi_scs_solver* s) { return s->sys; }
 uint32_t scs_solver_inputs(const zkmi_scs_solver* s) { return s->n_inputs; }
+uint32_t scs_solver_steps(const zkmi_scs_solver* s) { return s->n_steps; }
+size_t scs_solver_commits(const zkmi_scs_solver* s) { return s->commits.size(); }
+ScsSolverCommit scs_solver_commit(const zkmi_scs_solver* s, size_t i) {
+  const ScsPlan::Commit& c = s->commits[i];
+  return ScsSolverCommit{c.step, c.wire, (uint32_t)c.wires.size(), c.wires.data(), s->commit_wires[i]};
+}
 
-int scs_solver_run(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs, size_t batch, size_t Bp,
-                   Fr* staged, Fr* w, int32_t* status) {
+int scs_solver_stage(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs, size_t batch, size_t Bp,
+                     Fr* staged, Fr* w) {
   int rc;
   if (s->n_inputs) {
     if ((rc = stage_rows(ctx, inputs, s->n_inputs, batch, Bp, staged))) return rc;
     hipLaunchKernelGGL(scs_solve_init_kernel, dim3((unsigned)(Bp / 64), std::min<uint32_t>(s->n_inputs, 4096)),
                        dim3(64), 0, ctx->stream, (const Fr*)staged, s->input_wire, w, s->n_inputs, Bp);
+    ZK_HIP(hipGetLastError());
   }
+  return ZKMI_OK;
+}
+// steps [begin, end) of a plan under ZKMI_HINTS_STD, between the boundaries of its commitments
+int scs_solver_run_steps(zkmi_ctx* ctx, const zkmi_scs_solver* s, Fr* w, int32_t* status, size_t Bp,
+                         uint32_t begin, uint32_t end) {
+  if (begin > end || end > s->n_steps ||
+      !scs_std_launch(ctx->stream, s->S, s->records, s->coefs, s->outs, w, status, Bp, begin, end)) {
+    ctx->err = "scs solver: a step range outside the plan, or lanes_per_proof is no power of two, 1 .. 64";
+    return ZKMI_ERR_ARG;
+  }
+  ZK_HIP(hipGetLastError());
+  return ZKMI_OK;
+}
+
+int scs_solver_run(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs, size_t batch, size_t Bp,
+                   Fr* staged, Fr* w, int32_t* status) {
+  int rc;
+  if ((rc = scs_solver_stage(ctx, s, inputs, batch, Bp, staged, w))) return rc;
+  if (s->std_records) return scs_solver_run_steps(ctx, s, w, status, Bp, 0, s->n_steps);
   decltype(&launch_scs_solve<1>) launch;
   switch (s->S) {
     case 1: launch = launch_scs_solve<1>; break;
@@ -250,7 +281,7 @@ static int solver_load(zkmi_ctx* ctx, const zkmi_scs* m, const zkmi_scs_solver_d
   in.sel = sel.data();
   in.desc = &hd;
   ScsPlan plan;
-  const std::string err = scs_plan_build(in, &plan);
+  const std::string err = scs_plan_build(in, &plan, ZKMI_HINTS_STD);
   if (!err.empty()) {
     ctx->err = err;
     return ZKMI_ERR_ARG;
@@ -281,6 +312,12 @@ static int solver_load(zkmi_ctx* ctx, const zkmi_scs* m, const zkmi_scs_solver_d
     s->sys->hx[c] = m->hx[c];
     ok = upload(&s->sys->x[c], m->x[c], ng);
   }
+  s->std_records = plan.std_records;
+  s->commits = plan.commits;
+  for (size_t i = 0; ok && i < s->commits.size(); i++) {
+    s->commit_wires.push_back(nullptr);
+    ok = upload(&s->commit_wires.back(), s->commits[i].wires.data(), s->commits[i].wires.size());
+  }
   if (!ok) {
     ctx->err = "scs solver: device upload failed";
     zkmi_scs_solver_free(ctx, s);
@@ -305,6 +342,8 @@ void zkmi_scs_solver_free(zkmi_ctx* ctx, zkmi_scs_solver* s) {
   if (s->coefs) hipFree(s->coefs);
   if (s->outs) hipFree(s->outs);
   if (s->input_wire) hipFree(s->input_wire);
+  for (uint32_t* p : s->commit_wires)
+    if (p) hipFree(p);
   zkmi_scs_free(ctx, s->sys);
   delete s;
 }

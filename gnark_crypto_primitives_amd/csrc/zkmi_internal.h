@@ -297,6 +297,23 @@ const zkmi_scs* scs_solver_system(const zkmi_scs_solver* s);
 uint32_t scs_solver_inputs(const zkmi_scs_solver* s);
 int scs_solver_run(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs, size_t batch, size_t Bp,
                    Fr* staged, Fr* w, int32_t* status);
+// The same in pieces, for a plan with commitment hints (ZKMI_HINTS_STD; scs_plan.h): the inputs, then
+// the steps [begin, end) between the boundaries.  Commitment hint i: the first step of its barrier
+// level, its wire, its committed wires in operand order on the host and on the device.
+struct ScsSolverCommit {
+  uint32_t step, wire, n_wires;
+  const uint32_t *wires, *wires_dev;
+};
+uint32_t scs_solver_steps(const zkmi_scs_solver* s);
+size_t scs_solver_commits(const zkmi_scs_solver* s);
+ScsSolverCommit scs_solver_commit(const zkmi_scs_solver* s, size_t i);
+int scs_solver_stage(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs, size_t batch, size_t Bp,
+                     Fr* staged, Fr* w);
+int scs_solver_run_steps(zkmi_ctx* ctx, const zkmi_scs_solver* s, Fr* w, int32_t* status, size_t Bp,
+                         uint32_t begin, uint32_t end);
+// scs_solve_std.hip: steps [begin, end) of a plan on scs_std_kernel<S>; false: S is no lane count
+bool scs_std_launch(hipStream_t stream, uint32_t S, const uint4* recs, const Fr* coefs, const uint32_t* outs,
+                    Fr* w, int32_t* status, size_t Bp, uint32_t begin, uint32_t end);
 
 // RAII staging of a caller buffer (host or device) as device memory
 struct Staged {

@@ -253,7 +253,7 @@ class ScsCircuit:
             self._wiring = (cols[0], cols[1], cols[2], n_pub + 1 + len(rest))
         return self._wiring
 
-    def solver_description(self):
+    def solver_description(self, hints="basic"):
         """The gnark-shaped description of the solve (zkmi_scs_solver_desc), in the numbering of
         ``wiring()``: a dict with ``n_wires``, ``input_wire`` [n_inputs] (0xFFFFFFFF: nothing reads
         the input), ``instr`` [n_instr, 2] ((0, gate) | (1, hint), the program order before
@@ -264,9 +264,21 @@ class ScsCircuit:
         one exception is an OP_PAIR value without such a row (IsZero's batched inverse-or-zero, whose
         first gate has a second unknown): it is the InvZero hint it stands for, placed in front of
         that gate.  Any other hint raises.  A hint operand or output no gate touches gets a wire behind those of
-        ``wiring()``, so ``n_wires`` here may exceed wiring()'s."""
-        if getattr(self, "_solver_desc", None) is not None:
-            return self._solver_desc
+        ``wiring()``, so ``n_wires`` here may exceed wiring()'s.
+
+        ``hints="std"`` (ZKMI_HINTS_STD; the dict's ``hint_set`` is then 1, else 0) exports four more
+        kinds, each with the constant parameter p0 as its first input: OP_BITS with a limb width as
+        limbs (kind 3, p0 = width), OP_HIST with its OP_HQ queries as lookup multiplicities (kind 4,
+        p0 = table size), OP_BXOR / OP_BAND as byte operations (kind 6, p0 = 1 / 2) and the OP_COMMIT
+        unit as a commitment hint (kind 5, p0 = index, then the committed wires in the order of the
+        commitment's rows), which stands in front of its commitment row's gate.  OP_EMUL raises under
+        both."""
+        if hints not in ("basic", "std"):
+            raise ValueError("hints: 'basic' or 'std'")
+        std = hints == "std"
+        cache = self.__dict__.setdefault("_solver_descs", {})
+        if hints in cache:
+            return cache[hints]
         names = {OP_HIST: "OP_HIST (lookup multiplicities)", OP_HQ: "OP_HQ (a lookup query)",
                  OP_COMMIT: "OP_COMMIT (api.Commit)", OP_EMUL: "OP_EMUL (the emulated product)",
                  OP_BXOR: "OP_BXOR (byte xor)", OP_BAND: "OP_BAND (byte and)",
@@ -286,11 +298,16 @@ class ScsCircuit:
 
         instr, kinds, in_ptr, in_wire, in_coef, out_ptr, outs = [], [], [0], [], [], [0], []
 
-        def hint(kind, a, out_vals):
+        def hint(kind, a, out_vals, p0=None):
+            """a: the operand value, or the list of them; p0: the constant parameter in front"""
             instr.append((1, len(kinds)))
             kinds.append(kind)
-            in_wire.append(wire(a))
-            in_coef.append(1)
+            if p0 is not None:
+                in_wire.append(0xFFFFFFFF)
+                in_coef.append(p0)
+            for v in (a if isinstance(a, list) else [a]):
+                in_wire.append(wire(v))
+                in_coef.append(1)
             in_ptr.append(len(in_wire))
             outs.extend(wire(v) for v in out_vals)
             out_ptr.append(len(outs))
@@ -298,7 +315,28 @@ class ScsCircuit:
         known = set(range(n_pub + 1)) | {v for v, w in self.cc._val_wire.items()
                                          if 1 <= w <= self.n_inputs}
         pairs = {}                                     # value of a pending OP_PAIR -> its operand
+        unit = None                                    # std: [kind, p0, out values, rows to come, operands]
         for i, (op, d, a, b) in enumerate(self._prog):
+            if std and unit is not None and op == OP_HQ:
+                unit[4].append(a)
+                unit[3] -= 1
+            elif std and op in (OP_HIST, OP_COMMIT):
+                unit = [4, b, list(range(d, d + b)), a, []] if op == OP_HIST else [5, b, [d], a, []]
+            elif std and op == OP_BITS and (b >> 16) > 1:
+                out_vals = [d + j for j in range(b & 0xffff)]
+                hint(3, a, out_vals, p0=b >> 16)
+                known.update(out_vals)
+            elif std and op in (OP_BXOR, OP_BAND):
+                hint(6, [a, b], [d], p0=1 if op == OP_BXOR else 2)
+                known.add(d)
+            if std and unit is not None:
+                if unit[3] == 0:
+                    hint(unit[0], unit[4], unit[2], p0=unit[1])
+                    known.update(unit[2])
+                    unit = None
+                continue
+            if std and (op in (OP_BXOR, OP_BAND) or (op == OP_BITS and (b >> 16) > 1)):
+                continue
             if op == OP_ABC:
                 unknown = {v for v in (d, a, b) if v not in known}
                 if len(unknown) > 1:
@@ -314,7 +352,9 @@ class ScsCircuit:
                 pairs[d] = a
             elif op in names:
                 raise ValueError(f"solver_description: the circuit holds {names[op]}, which the "
-                                 "basic hint set (InvZero, NBits) does not cover")
+                                 + ("std hint set (limbs, lookup multiplicities, commitment, byte "
+                                    "operations) does not cover" if std else
+                                    "basic hint set (InvZero, NBits) does not cover"))
             # every other op is a gate (its OP_ABC row follows) or a division a gate defines
         val_of = {}
         for v, w in self.cc._val_wire.items():
@@ -322,13 +362,14 @@ class ScsCircuit:
                 val_of[w] = v
         input_wire = [wire_of.get(val_of.get(1 + i), 0xFFFFFFFF) for i in range(self.n_inputs)]
         u32 = lambda x, shape=(-1,): np.array(x, dtype=np.uint32).reshape(shape)
-        self._solver_desc = {
+        cache[hints] = {
+            "hint_set": 1 if std else 0,
             "n_wires": n_wires, "input_wire": u32(input_wire), "instr": u32(instr, (-1, 2)),
             "hint_kind": u32(kinds), "hint_in_ptr": u32(in_ptr), "hint_in_wire": u32(in_wire),
             "hint_in_coef": list(in_coef), "hint_out_ptr": u32(out_ptr), "hint_out": u32(outs)}
-        return self._solver_desc
+        return cache[hints]
 
-    def solve_description(self, desc, inputs):
+    def solve_description(self, desc, inputs, commit_fn=None):
         """Plain-Python interpreter of a solver description: the statement of what
         zkmi_scs_solve_batch computes and the CPU reference of its tests.  One walk over ``instr``
         with a solved-wire bitmap that starts with the inputs' wires (ONE is not special: its gate
@@ -337,6 +378,12 @@ class ScsCircuit:
         x = -rest / k with k the sum of the linear selectors on u's positions; where u is exactly one
         of a, b and qM != 0, x = -rest / (k + qM other), a zero divisor flagging the proof.  Hints:
         InvZero (1 / v, 0 for v = 0) and NBits (output i = bit i of v), v = coef * wire or coef.
+        The kinds of ZKMI_HINTS_STD, with the constant p0 as their first input: limbs (3: output j =
+        bits [j p0, (j + 1) p0) of v), lookup multiplicities (4: output j = the number of queries
+        equal to j, a query >= p0 counting nowhere), commitment (5: ``commit_fn(index, committed
+        values)``, or the SHA-256 stand-in of ``_commit_value``) and byte operations (6: p0 = 1 XOR, 2
+        AND on the low 32 bits).  The rows of the commitments (``self.commitments``) hold by
+        construction and take no part in the gate check.
         inputs: n_inputs integers, public first.  Returns (wires, status): desc["n_wires"] integers
         and 0 or -5 (a zero divisor, or a gate that does not hold)."""
         xs = [x.tolist() for x in self.wiring()[:3]]
@@ -351,6 +398,47 @@ class ScsCircuit:
         kinds, ip, op_ = desc["hint_kind"].tolist(), desc["hint_in_ptr"].tolist(), desc["hint_out_ptr"].tolist()
         hw, hc, ho = desc["hint_in_wire"].tolist(), desc["hint_in_coef"], desc["hint_out"].tolist()
         for ii, (kind, idx) in enumerate(desc["instr"].tolist()):
+            if kind == 1 and kinds[idx] in (3, 4, 5, 6):
+                ts = list(range(ip[idx], ip[idx + 1]))
+                o = ho[op_[idx]:op_[idx + 1]]
+                if not ts or hw[ts[0]] != 0xFFFFFFFF:
+                    raise ValueError(f"instruction {ii}: the parameter p0 must be a constant")
+                for t in ts[1:]:
+                    if hw[t] != 0xFFFFFFFF and not solved[hw[t]]:
+                        raise ValueError(f"instruction {ii}: reads wire {hw[t]}, which is not solved yet")
+                if any(solved[x] for x in o):
+                    raise ValueError(f"instruction {ii}: an output wire is already solved")
+                p0 = hc[ts[0]] % R
+                vals = [hc[t] * (w[hw[t]] if hw[t] != 0xFFFFFFFF else 1) % R for t in ts[1:]]
+                hk = kinds[idx]
+                if hk == 3:
+                    if len(vals) != 1 or not 1 <= p0 <= 64:
+                        raise ValueError(f"instruction {ii}: limbs take a width in 1 .. 64 and one value")
+                    for j, x in enumerate(o):
+                        w[x] = (vals[0] >> (j * p0)) & ((1 << p0) - 1)
+                elif hk == 4:
+                    if p0 != len(o):
+                        raise ValueError(f"instruction {ii}: the table size is not the number of outputs")
+                    for j, x in enumerate(o):
+                        w[x] = sum(1 for v in vals if v == j)
+                elif hk == 6:
+                    if len(vals) != 2 or len(o) != 1 or p0 not in (1, 2):
+                        raise ValueError(f"instruction {ii}: a byte operation takes 1 | 2 and two values")
+                    u, v = vals[0] & 0xffffffff, vals[1] & 0xffffffff
+                    w[o[0]] = u ^ v if p0 == 1 else u & v
+                else:
+                    if len(o) != 1 or not vals:
+                        raise ValueError(f"instruction {ii}: a commitment has operands and one output")
+                    if commit_fn is not None:
+                        w[o[0]] = int(commit_fn(p0, vals)) % R
+                    else:
+                        h = hashlib.sha256(b"stand-in plonk commitment %d" % p0)
+                        for v in vals:
+                            h.update(int(v).to_bytes(32, "big"))
+                        w[o[0]] = int.from_bytes(h.digest(), "big") % R
+                for x in o:
+                    solved[x] = True
+                continue
             if kind == 1:
                 if kinds[idx] not in (1, 2) or ip[idx + 1] - ip[idx] != 1:
                     raise ValueError(f"instruction {ii}: not an InvZero or NBits hint with one input")
@@ -403,8 +491,11 @@ class ScsCircuit:
             raise ValueError("a gate occurs in no instruction")
         if not all(solved):
             raise ValueError(f"wire {solved.index(False)} is still unsolved")
+        held = {r for c in getattr(self, "commitments", []) for r in list(c["rows"]) + [c["row"]]}
         for g, (_, _, _, qL, qR, qO, qM, qC) in enumerate(self.gates):
             a, b, c = w[xs[0][g]], w[xs[1][g]], w[xs[2][g]]
+            if g in held:
+                continue
             if (qL * a + qR * b + qO * c + qM * a * b + qC - (a if g < n_pub else 0)) % R:
                 status = -5
         return w, status

@@ -165,6 +165,7 @@ SYMBOLS = [
     ("zkmi_scs_solve_batch", _I, [_P, _P, _P, _SZ, _P, _P]),
     ("zkmi_plonk_round1_scs", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P]),
     ("zkmi_plonk_prove_scs", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
+    ("zkmi_plonk_prove_scs_ex", _I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
 ]
 
 _lib = None

@@ -562,14 +562,23 @@ class WitnessProver:
 
     proofs_of = staticmethod(Prover.proofs_of)
 
-    def load_solver(self, lanes_per_proof=0, desc=None):
+    def load_solver(self, lanes_per_proof=0, desc=None, hints=None):
         """The gnark-shaped solver of the system (zkmi_scs_solver_load): ``prove_raw(blind,
         inputs=...)`` and ``solve`` then need no host solver.  desc: what
         ``ScsCircuit.solver_description()`` returns (the system's own by default).  The description
         may number wires behind those of ``wiring()`` (hint operands no gate touches): the solver
-        gets the system with that many wires.  Replaces a solver loaded before; returns its handle."""
+        gets the system with that many wires.  Replaces a solver loaded before; returns its handle.
+        hints: "basic" (InvZero, NBits) or "std" (ZKMI_HINTS_STD: limbs, lookup multiplicities,
+        commitment, byte operations): the set of the system's own description and the ``hint_set``
+        the loader gets; left out, a description's own "hint_set" entry holds (0 without one)."""
         ctx, system = self.ctx, self.system
-        d = system.solver_description() if desc is None else desc
+        if hints not in (None, "basic", "std"):
+            raise ValueError("hints: 'basic' or 'std'")
+        if desc is None:
+            d = system.solver_description() if hints is None else system.solver_description(hints)
+        else:
+            d = desc
+        hint_set = int(d.get("hint_set", 0)) if hints is None else int(hints == "std")
         n_wires = int(d["n_wires"])
         if n_wires < self.n_wires:
             raise ValueError("the description has fewer wires than the system")
@@ -579,7 +588,7 @@ class WitnessProver:
         arrs = [u32(d[k]) for k in ("input_wire", "instr", "hint_kind", "hint_in_ptr", "hint_in_wire")]
         arrs += [np.ascontiguousarray(coef), u32(d["hint_out_ptr"]), u32(d["hint_out"])]
         sd = _lib.ScsSolverDesc(len(arrs[0]), arrs[0].ctypes.data, arrs[1].size // 2, len(arrs[2]),
-                                *[a.ctypes.data for a in arrs[1:]], lanes_per_proof, 0)
+                                *[a.ctypes.data for a in arrs[1:]], lanes_per_proof, hint_set)
         scs_h = self.scs_h
         if n_wires != self.n_wires:
             sel = np.ascontiguousarray(self._keep[0][:, :self.n_gates])
@@ -653,13 +662,23 @@ class WitnessProver:
         numpy array, pageable or from Context.host_alloc, or a device tensor); or columns = (a, b,
         c), [batch, n_gates, 4] each, taken as they are.  Returns (records, status) as
         Prover.prove_raw does; for a key with commitments, with blind_commit, (records, status,
-        commit records) through zkmi_plonk_prove_witness_ex."""
+        commit records) through zkmi_plonk_prove_witness_ex, or, from inputs, through
+        zkmi_plonk_prove_scs_ex (a solver loaded with hints="std" whose commitment hints are the
+        key's commitments)."""
         batch, wit, _ = self._args(blind, wires, columns, inputs)
         blind = np.ascontiguousarray(blind)
         rec = np.zeros((batch, 96), dtype=np.uint64)
         status = np.zeros(batch, dtype=np.int32)
         vkd = (C.c_uint8 * 32).from_buffer_copy(self.pk.vk_digest)
         n_c = len(self.pk.commitments)
+        if inputs is not None and n_c:
+            blind_commit = _blind_commit(blind_commit, batch, n_c)
+            cm = np.zeros((batch, n_c, 12), dtype=np.uint64)
+            self.ctx._check(self.ctx.lib.zkmi_plonk_prove_scs_ex(
+                self.ctx.h, self.pk_h, self.solver_h, _lib._ptr(wit), batch, blind.ctypes.data,
+                blind_commit.ctypes.data, vkd, rec.ctypes.data, cm.ctypes.data, status.ctypes.data),
+                "zkmi_plonk_prove_scs_ex")
+            return rec, status, cm
         if inputs is not None:
             self.ctx._check(self.ctx.lib.zkmi_plonk_prove_scs(
                 self.ctx.h, self.pk_h, self.solver_h, _lib._ptr(wit), batch, blind.ctypes.data, vkd,

@@ -674,7 +674,20 @@ int zkmi_plonk_prove_witness_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs
  * ONE wire is not special, its gate qL x - 1 = 0 solves it) and finds each gate's one unknown
  * (csrc/scs_plan.h).  A hint input is a single term, coef * wire or a constant,
  * because a variable of gnark's scs builder is a single term [UPSTREAM-RECALL]; parity unpinned.
- * Hints: ZKMI_HINT_INVZERO and ZKMI_HINT_NBITS; kinds 3 .. 7 are refused by name. */
+ * Hints: ZKMI_HINT_INVZERO and ZKMI_HINT_NBITS under hint_set = ZKMI_HINTS_BASIC, where kinds 3 .. 7
+ * are refused by name.  Under hint_set = ZKMI_HINTS_STD additionally kinds 3 .. 6, each input still a
+ * single term and the first one the constant parameter p0:
+ *   ZKMI_HINT_LIMBS   p0 = width (1 .. 64), one value; output j = bits [j width, (j + 1) width) of its
+ *                     canonical value, bits from 256 on are 0
+ *   ZKMI_HINT_COUNT   p0 = table size = number of outputs, then the queries; output j = the number of
+ *                     queries equal to j, a query >= size counts nowhere
+ *   ZKMI_HINT_COMMIT  p0 = the commitment's index (0, 1, .. in instruction order, at most
+ *                     ZKMI_PLONK_MAX_COMMITMENTS), then the committed wires in the order of the key's
+ *                     `rows`, each a wire with coefficient 1; one output, the commitment wire.  The hint
+ *                     stands in front of the gate of its commitment row.  Its value needs the key:
+ *                     zkmi_plonk_prove_scs_ex
+ *   ZKMI_HINT_BYTEOP  p0 = 1 XOR | 2 AND, two values; one output, the operation on their low 32 bits
+ * Kind 7 (the emulated product) is refused by name under both sets, and so is every other hint_set. */
 typedef struct {
   uint32_t n_inputs;            /* values per proof, public first: the inputs of zkmi_plonk_prove */
   const uint32_t* input_wire;   /* n_inputs: wire each input lands on; 0xFFFFFFFF = no gate reads it */
@@ -687,8 +700,8 @@ typedef struct {
   const uint32_t* hint_out_ptr; /* n_hints + 1 */
   const uint32_t* hint_out;
   uint32_t lanes_per_proof;     /* power of two 1..64; 0 = auto */
-  uint32_t hint_set;            /* 0 = ZKMI_HINTS_BASIC; anything else refused, naming the field.  The
-                                   last field: it takes the values a later hint set defines */
+  uint32_t hint_set;            /* ZKMI_HINTS_BASIC (0) or ZKMI_HINTS_STD (1); anything else refused, naming
+                                   the sets.  The last field: it takes the values a later set defines */
 } zkmi_scs_solver_desc;
 typedef struct zkmi_scs_solver zkmi_scs_solver;
 /* Builds and checks the solve plan on the host and uploads it with a copy of the system; the system
@@ -704,20 +717,35 @@ int zkmi_scs_solver_info(const zkmi_scs_solver* solver, uint64_t* info /* 8 */);
 /* The witness solve alone: inputs = batch x n_inputs fr (Montgomery, proof-major, host or device) ->
  * wires_out = batch x n_wires fr (may be NULL), status_out = per proof 0 or ZKMI_ERR_UNSATISFIED (a
  * solve divides by zero, or a gate does not hold: every gate is checked afterwards, so the status is
- * what zkmi_plonk_prove_witness reports for the same wires). */
+ * what zkmi_plonk_prove_witness reports for the same wires).  A solver whose plan holds commitment
+ * hints is refused: their values need a proving key (zkmi_plonk_prove_scs_ex). */
 int zkmi_scs_solve_batch(zkmi_ctx* ctx, const zkmi_scs_solver* solver, const void* inputs, size_t batch,
                          void* wires_out, int32_t* status_out);
 /* zkmi_plonk_round1_witness / zkmi_plonk_prove_witness (wire form) with the wires solved on the GPU
  * from the inputs: same columns, same transcript, same records.  Refused before anything is queued:
  * a key with commitments, an n_public that differs from the key's, batch outside [1, max_batch], more
  * wires than the 4n work buffer holds and, for a trace-loaded key, a wiring that contradicts the
- * key's permutation. */
+ * key's permutation, a solver whose plan holds commitment hints. */
 int zkmi_plonk_round1_scs(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver* solver,
                           const void* inputs, size_t batch, const void* blind, void* commits_out,
                           int32_t* status_out);
 int zkmi_plonk_prove_scs(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver* solver,
                          const void* inputs, size_t batch, const void* blind, const uint8_t* vk_digest,
                          void* proofs_out, int32_t* status_out);
+/* zkmi_plonk_prove_scs for keys with commitments, the twin of zkmi_plonk_prove_witness_ex (blind_commit
+ * and commit_out as there): a solver loaded with ZKMI_HINTS_STD whose commitment hints are the key's
+ * commitments one by one.  The solve stops at each commitment's boundary, the commitment is formed
+ * from the committed wires and hashed, H_i goes into the commitment wire, and the solve goes on; the
+ * wire-form path follows unchanged.  Refused before anything is queued: what zkmi_plonk_prove_scs
+ * refuses (but for the key's commitments), a number of commitment hints that differs from the key's
+ * commitments, a hint whose committed wires are not xa[rows[j]] of the key's commitment in order or
+ * whose output is not xa[row].  With a key without commitments, a solver without commitment hints and
+ * both pointers NULL it returns what zkmi_plonk_prove_scs returns.  status_out: the OR of a zero
+ * divisor, the gate check and the commitment check. */
+int zkmi_plonk_prove_scs_ex(zkmi_ctx* ctx, zkmi_plonk_pk* pk, const zkmi_scs_solver* solver,
+                            const void* inputs, size_t batch, const void* blind, const void* blind_commit,
+                            const uint8_t* vk_digest, void* proofs_out, void* commit_out,
+                            int32_t* status_out);
 
 /* Per-stage device time of the last zkmi_prove_collect / zkmi_prove_batch in milliseconds, from
  * HIP events on the library's streams: [0] solve (stage 1, second stream), [1] quotient (NTTs +

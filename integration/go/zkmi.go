@@ -261,7 +261,9 @@ var hintKinds = map[string]uint32{
 	"github.com/consensys/gnark/std/math/emulated.mulHint":                        C.ZKMI_HINT_EMULMUL, // [UPSTREAM-RECALL]
 }
 
-// HintSet names the hint kinds a solver accepts (enum zkmi_hint_set).
+// HintSet names the hint kinds a solver accepts (enum zkmi_hint_set).  The PLONK solver
+// (zkmi_scs_solver_desc.hint_set, for which this file has no binding yet) takes HintsBasic and
+// HintsStd; under HintsStd a key with commitments is proved through zkmi_plonk_prove_scs_ex.
 type HintSet uint32
 
 const (

@@ -1,0 +1,325 @@
+"""Host build of csrc/scs_plan.h under ZKMI_HINTS_STD: tests/native/scs_plan_std_check.cpp builds the
+plan of a hand-written description for every number of sub-lanes 0 (auto), 1 .. 64, asserts the
+plan's two guarantees on every step -- a lookup count's three phases and the boundaries of the
+commitment hints with them -- and interprets it with scs_record_run.  Checked here: the wires against
+the Python reference (ScsCircuit.solve_description), the boundaries, every new refusal, and that a
+description without a std kind gives the same plan under both sets.  The program is built plain and
+with -fsanitize=address,undefined; the two builds must print the same."""
+import os
+import random
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from gnark_crypto_primitives_amd.frontend.compile import to_mont_array
+from gnark_crypto_primitives_amd.frontend.scs import ScsCircuit
+from tests import helpers as H
+from tests.test_native_scs_plan import ORDER, POW2, LANES_MSG, Hand, dump_of, hand_inputs, words
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+R = H.R
+NONE = 0xFFFFFFFF
+
+
+class HandStd:
+    """A hand-written system for the hints of ZKMI_HINTS_STD.  Inputs: the public p (wire 0), s
+    (wire 1), t (wire 2) and one that no gate reads.
+      limbs      width 8 of s, 5 outputs; width 64 of 3 t, 5 outputs (the last one lies past bit 256)
+      counts     a table of 17 (one chunk of 16 and 1) with 7 queries -- limbs (mostly >= 17: they
+                 count nowhere), the constant 5, 2 * ONE, ONE --; a table of 5 on the same levels
+                 with a query >= its size; a table of 2 with no query
+      byte ops   XOR of s and 5 t (field elements: bits above 32 set), AND of a 64-bit limb and a
+                 48-bit constant
+      commitments (``commits=True``): 0 over inputs only (its first range of steps is empty), 1 over
+                 the first one's wire and a wire deep in the solve, 2 over the last wire solved
+                 (nothing depends on it: the last range is empty)"""
+    n_public = 2          # counting ONE
+    BASE = [(0, 0, 0, 1, 0, 0, 0, 0),               # public input p = wire 0
+            (3, 3, 3, 1, 0, 0, 0, -1),              # ONE = wire 3
+            (38, 39, 40, 1, 1, -1, 0, 0),           # w40 = xor + and
+            (40, 14, 41, 0, 0, -1, 1, 0)]           # w41 = w40 * (count of 0 in the table of 17)
+    COMMIT = [(1, 1, 1, -1, 0, 0, 0, 0), (2, 2, 2, -1, 0, 0, 0, 0),      # rows 4, 5: C_0
+              (42, 42, 42, -1, 0, 0, 0, 0),                              # row 6: r_0, wire 42
+              (42, 42, 42, -1, 0, 0, 0, 0), (41, 41, 41, -1, 0, 0, 0, 0),  # rows 7, 8: C_1
+              (43, 43, 43, -1, 0, 0, 0, 0),                              # row 9: r_1, wire 43
+              (43, 42, 44, 1, 1, -1, 0, 0),                              # row 10: w44 = w43 + w42
+              (44, 44, 44, -1, 0, 0, 0, 0),                              # row 11: C_2
+              (45, 45, 45, -1, 0, 0, 0, 0)]                              # row 12: r_2, wire 45
+
+    def __init__(self, commits=True):
+        self.with_commits = commits
+        self.gates = self.BASE + (self.COMMIT if commits else [])
+        self.n_gates = len(self.gates)
+        self.n_wires = 46 if commits else 42
+        self.commitments = [{"rows": [4, 5], "row": 6}, {"rows": [7, 8], "row": 9},
+                            {"rows": [11], "row": 12}] if commits else []
+        col = lambda j: np.array([g[j] % R for g in self.gates], dtype=object)
+        self.qL, self.qR, self.qO, self.qM, self.qC = (col(j) for j in (3, 4, 5, 6, 7))
+        # (kind, [(wire | NONE, coefficient)], outputs)
+        self.hints = [
+            (3, [(NONE, 8), (1, 1)], list(range(4, 9))),
+            (3, [(NONE, 64), (2, 3)], list(range(9, 14))),
+            (4, [(NONE, 17), (4, 1), (5, 1), (6, 1), (NONE, 5), (3, 2), (3, 1), (8, 1)], list(range(14, 31))),
+            (4, [(NONE, 5), (3, 1), (3, 1), (NONE, 7), (3, 4)], list(range(31, 36))),
+            (4, [(NONE, 2)], [36, 37]),
+            (6, [(NONE, 1), (1, 1), (2, 5)], [38]),
+            (6, [(NONE, 2), (9, 1), (NONE, 0xFFFF0000FFFF)], [39])]
+        self.instr = [(0, 0), (0, 1)] + [(1, h) for h in range(7)] + [(0, 2), (0, 3)]
+        if commits:
+            self.hints += [(5, [(NONE, 0), (1, 1), (2, 1)], [42]), (5, [(NONE, 1), (42, 1), (41, 1)], [43]),
+                           (5, [(NONE, 2), (44, 1)], [45])]
+            self.instr += [(0, 4), (0, 5), (1, 7), (0, 6), (0, 7), (0, 8), (1, 8), (0, 9), (0, 10), (0, 11),
+                           (1, 9), (0, 12)]
+
+    def wiring(self):
+        x = [np.array([g[j] for g in self.gates], dtype=np.uint32) for j in range(3)]
+        return x[0], x[1], x[2], self.n_wires
+
+    solve_description = ScsCircuit.solve_description
+
+    def description(self, hints=None, instr=None, n_wires=None):
+        hints = self.hints if hints is None else hints
+        u32 = lambda x: np.array(x, dtype=np.uint32)
+        in_ptr, out_ptr = [0], [0]
+        for _, ins, outs in hints:
+            in_ptr.append(in_ptr[-1] + len(ins))
+            out_ptr.append(out_ptr[-1] + len(outs))
+        return {"hint_set": 1, "n_wires": self.n_wires if n_wires is None else n_wires,
+                "input_wire": u32([0, 1, 2, NONE]),
+                "instr": u32(self.instr if instr is None else instr).reshape(-1, 2),
+                "hint_kind": u32([k for k, _, _ in hints]), "hint_in_ptr": u32(in_ptr),
+                "hint_in_wire": u32([w for _, ins, _ in hints for w, _ in ins]),
+                "hint_in_coef": [c for _, ins, _ in hints for _, c in ins],
+                "hint_out_ptr": u32(out_ptr), "hint_out": u32([o for _, _, outs in hints for o in outs])}
+
+    def skip_rows(self):
+        return [r for c in self.commitments for r in c["rows"] + [c["row"]]]
+
+
+def stand_in(i, vals):
+    """the challenge scs_plan_std_check.cpp gives commitment i"""
+    return (1 + i + sum((j + 1) * v for j, v in enumerate(vals))) % R
+
+
+def std_inputs(rng):
+    return [rng.randrange(R), rng.randrange(R), rng.randrange(R), rng.randrange(R)]
+
+
+@pytest.fixture(scope="module")
+def builds(tmp_path_factory):
+    d = tmp_path_factory.mktemp("scs_std_plan")
+    out = []
+    for name, flags in (("plain", ["-O2"]),
+                        ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined",
+                                       "-fno-sanitize-recover=all"])):
+        exe = str(d / ("scs_plan_std_check_" + name))
+        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
+                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
+                               os.path.join(ROOT, "tests", "native", "scs_plan_std_check.cpp"),
+                               "-o", exe])
+        out.append(exe)
+    return d, out
+
+
+def std_dump(system, desc, inputs, hint_set=1):
+    d = dump_of(system, desc, inputs)
+    d["header"][5] = hint_set
+    d["skip_rows"] = np.array(system.skip_rows() if hasattr(system, "skip_rows") else [], dtype=np.uint32)
+    return d
+
+
+def run(builds, dump, s_first, s_last, tag="case"):
+    """(stdout by S, [(S, [(status, wires [n_wires, 4])])]) -- the same from both builds"""
+    d, exes = builds
+    src = str(d / (tag + ".in"))
+    with open(src, "wb") as f:
+        for name in ORDER + ("skip_rows",):
+            a = np.ascontiguousarray(dump[name], dtype=np.uint32)
+            f.write(np.uint32(a.size).tobytes())
+            f.write(a.tobytes())
+    got = []
+    for exe in exes:
+        dst = str(d / (tag + ".out"))
+        p = subprocess.run([exe, src, dst, str(s_first), str(s_last)], text=True, capture_output=True)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+        got.append((p.stdout, open(dst, "rb").read()))
+    assert got[0] == got[1], "the plain and the sanitized build disagree"
+    lines = {}
+    for line in got[0][0].splitlines():
+        head, rest = line.split(" ", 1)
+        lines[int(head[2:])] = rest
+    assert sorted(lines) == list(range(s_first, s_last + 1))
+    w = np.frombuffer(got[0][1], dtype=np.uint32)
+    n_wires, plans, o = int(dump["header"][0]), [], 0
+    while o < w.size:
+        S, batch = int(w[o]), int(w[o + 1])
+        o += 2
+        sol = []
+        for _ in range(batch):
+            sol.append((int(w[o:o + 1].view(np.int32)[0]),
+                        w[o + 1:o + 1 + 8 * n_wires].view(np.uint64).reshape(n_wires, 4)))
+            o += 1 + 8 * n_wires
+        plans.append((S, sol))
+    return lines, plans
+
+
+def test_the_reference_itself():
+    """spot values of the hand description worked out by hand"""
+    hand = HandStd()
+    p, s, t, _ = inp = [7, (1 << 200) + 0x0302010011, R - 1, 9]
+    w, st = hand.solve_description(hand.description(), inp, commit_fn=stand_in)
+    assert st == 0 and w[4:9] == [0x11, 0x00, 0x01, 0x02, 0x03]
+    v = 3 * t % R
+    assert w[9:13] == [(v >> (64 * j)) & ((1 << 64) - 1) for j in range(4)] and w[13] == 0
+    # queries 0x11 -> 17 (outside), 0, 1, 5, 2, 1, 3
+    want = [0] * 17
+    for q in (0, 1, 5, 2, 1, 3):
+        want[q] += 1
+    assert w[14:31] == want
+    assert w[31:36] == [0, 2, 0, 0, 1] and w[36:38] == [0, 0]
+    assert w[38] == (s & 0xffffffff) ^ (5 * t % R & 0xffffffff)
+    assert w[39] == w[9] & 0xffffffff & 0xFFFF0000FFFF
+    assert w[40] == w[38] + w[39] and w[41] == w[40] * w[14]
+    assert w[42] == (1 + s + 2 * t) % R and w[43] == (2 + w[42] + 2 * w[41]) % R
+    assert w[44] == (w[43] + w[42]) % R and w[45] == (3 + w[44]) % R
+
+
+@pytest.mark.parametrize("commits", [True, False])
+def test_hand_description_every_lane_count(builds, commits):
+    rng = random.Random(21)
+    hand = HandStd(commits)
+    desc = hand.description()
+    inputs = [std_inputs(rng) for _ in range(3)]
+    inputs.append([1, 0, 0, 0])                       # s = t = 0: every limb is 0
+    lines, plans = run(builds, std_dump(hand, desc, inputs), 0, 64, "hand%d" % commits)
+    ref = [hand.solve_description(desc, x, commit_fn=stand_in) for x in inputs]
+    assert [st for _, st in ref] == [0] * 4
+    want = [to_mont_array(w) for w, _ in ref]
+    assert len(plans) == 8
+    for s in range(65):
+        if s and s not in POW2:
+            assert lines[s] == "error: " + LANES_MSG
+            continue
+        head, *groups = lines[s].split(" | ")
+        ok, lanes, records, steps, levels, inversions, std, _ = head.split()
+        assert ok == "ok" and std == "1" and (int(lanes) == s or (s == 0 and int(lanes) in (1, 2, 4, 8, 16)))
+        assert int(steps) >= int(levels) >= 1 and int(steps) * int(lanes) >= int(records)
+        # 5 + 5 limbs in two records, 7 + 4 queries, 2 + 1 + 1 chunks zeroed and as many read back,
+        # two byte operations, and the gates that solve a wire
+        assert int(records) == 2 + 11 + 8 + 2 + (3 if not commits else 4)
+        groups = [tuple(map(int, g.split())) for g in groups]
+        if not commits:
+            assert groups == []
+            continue
+        # (instruction, boundary, wire, committed wires): the first range is empty, the last one too
+        assert [(g[0], g[2], g[3]) for g in groups] == [(13, 42, 2), (17, 43, 2), (21, 45, 1)]
+        assert groups[0][1] == 0 < groups[1][1] < groups[2][1] == int(steps)
+    for S, sol in plans:
+        for i, (status, wires) in enumerate(sol):
+            assert status == 0, (S, i)
+            assert np.array_equal(wires, want[i]), (S, i)
+
+
+def test_a_wrong_input_is_flagged(builds):
+    """the public gate given a constant that it cannot hold with: the status is -5 from the plan's
+    interpretation as from the reference"""
+    hand = HandStd(False)
+    desc = hand.description()
+    hand.gates = list(hand.gates)
+    hand.gates[0] = (0, 0, 0, 1, 0, 0, 0, 1)       # the public gate no longer holds
+    hand.qC = np.array([g[7] % R for g in hand.gates], dtype=object)
+    inputs = [std_inputs(random.Random(3))]
+    assert hand.solve_description(desc, inputs[0])[1] == -5
+    _, plans = run(builds, std_dump(hand, desc, inputs), 4, 4, "flag")
+    assert plans[0][1][0][0] == -5
+
+
+def test_a_basic_description_gives_the_same_plan_under_both_sets(builds):
+    hand = Hand()
+    desc = hand.description()
+    inputs = [hand_inputs(random.Random(5))]
+    a, pa = run(builds, std_dump(hand, desc, inputs, 0), 0, 64, "basic0")
+    b, pb = run(builds, std_dump(hand, desc, inputs, 1), 0, 64, "basic1")
+    assert a == b and a[4].split()[0] == "ok" and a[4].split()[6] == "0"
+    assert all(np.array_equal(x[1][0][1], y[1][0][1]) for x, y in zip(pa, pb))
+
+
+def refusal(builds, dump, tag, lanes=4):
+    lines, plans = run(builds, dump, lanes, lanes, tag)
+    assert not plans
+    assert lines[lanes].startswith("error: scs solver: "), lines[lanes]
+    return lines[lanes][len("error: scs solver: "):]
+
+
+def test_refusals(builds):
+    hand = HandStd()
+    inputs = [std_inputs(random.Random(6))]
+
+    def with_hint(h, kind=None, ins=None, outs=None, **kw):
+        hints = list(hand.hints)
+        k, i, o = hints[h]
+        hints[h] = (k if kind is None else kind, i if ins is None else ins, o if outs is None else outs)
+        return std_dump(hand, hand.description(hints, **kw), inputs)
+
+    at = lambda h: "instruction %d (hint %d): " % (hand.instr.index((1, h)), h)
+    limbs, count, byteop, commit = "limbs (kind 3)", "lookup multiplicities (kind 4)", \
+        "byte operation (kind 6)", "commitment (kind 5)"
+    # operand and output counts
+    assert refusal(builds, with_hint(0, ins=[(NONE, 8), (1, 1), (2, 1)]), "l_in") == \
+        at(0) + limbs + " takes p0 = the width and one value, and has outputs"
+    assert refusal(builds, with_hint(0, ins=[(NONE, 8)]), "l_in1") == \
+        at(0) + limbs + " takes p0 = the width and one value, and has outputs"
+    assert refusal(builds, with_hint(5, ins=[(NONE, 1), (1, 1)]), "b_in") == \
+        at(5) + byteop + " takes p0 = the operation and two values, and has one output"
+    assert refusal(builds, with_hint(5, outs=[38, 39], kind=6), "b_out").startswith(at(5) + byteop + " takes p0")
+    assert refusal(builds, with_hint(7, ins=[(NONE, 0)]), "c_in") == \
+        at(7) + commit + " takes p0 = its index and the committed wires, and has one output"
+    assert refusal(builds, with_hint(4, ins=[]), "no_p0") == \
+        at(4) + count + " takes a parameter p0 as its first input"
+    # the parameter
+    for width in (0, 65, R - 1):
+        assert refusal(builds, with_hint(1, ins=[(NONE, width), (2, 3)]), "width") == \
+            at(1) + limbs + ": the width p0 must be in 1 .. 64"
+    assert refusal(builds, with_hint(2, ins=[(NONE, 16)] + hand.hints[2][1][1:]), "size") == \
+        at(2) + count + ": the table size p0 must be the number of outputs, 17"
+    assert refusal(builds, with_hint(3, ins=[(3, 5)] + hand.hints[3][1][1:]), "p0_wire") == \
+        at(3) + count + ": the parameter p0 reads wire 3; it must be a constant"
+    for op in (0, 3):
+        assert refusal(builds, with_hint(6, ins=[(NONE, op)] + hand.hints[6][1][1:]), "op") == \
+            at(6) + byteop + ": the operation p0 must be 1 (XOR) or 2 (AND)"
+    # commitment operands and indices
+    assert refusal(builds, with_hint(7, ins=[(NONE, 0), (1, 1), (2, 2)]), "c_coef") == \
+        at(7) + commit + ": operand 1 must be a wire with coefficient 1"
+    assert refusal(builds, with_hint(7, ins=[(NONE, 0), (NONE, 1), (2, 1)]), "c_const") == \
+        at(7) + commit + ": operand 0 must be a wire with coefficient 1"
+    assert refusal(builds, with_hint(8, ins=[(NONE, 2), (42, 1), (41, 1)]), "c_index") == \
+        at(8) + commit + ": the index p0 must count the commitment hints in instruction order, here 1"
+    assert refusal(builds, with_hint(7, ins=[(NONE, 1), (1, 1), (2, 1)]), "c_index0") == \
+        at(7) + commit + ": the index p0 must count the commitment hints in instruction order, here 0"
+    # nine commitments: six more, each with a wire of its own behind the system's
+    hints = list(hand.hints) + [(5, [(NONE, 3 + j), (1, 1)], [46 + j]) for j in range(6)]
+    instr = hand.instr + [(1, 10 + j) for j in range(6)]
+    d = std_dump(hand, hand.description(hints, instr, n_wires=52), inputs)
+    assert refusal(builds, d, "nine") == \
+        "instruction %d (hint 15): " % (len(instr) - 1) + commit + ": more than 8 commitments"
+    d = std_dump(hand, hand.description(hints[:-1], instr[:-1], n_wires=51), inputs)
+    assert run(builds, d, 4, 4, "eight")[0][4].startswith("ok ")
+    # a std hint reads an unsolved wire, writes a solved one
+    assert refusal(builds, with_hint(2, ins=hand.hints[2][1][:-1] + [(40, 1)]), "unsolved") == \
+        at(2) + "reads wire 40, which is not solved yet"
+    assert refusal(builds, with_hint(5, outs=[4]), "solved") == at(5) + "output wire 4 is already solved"
+    # kind 7 by name, an unknown kind, the hint sets
+    assert refusal(builds, with_hint(5, kind=7), "kind7") == \
+        at(5) + "hints emulated product (kind 7) are not supported on this entry"
+    assert refusal(builds, with_hint(5, kind=9), "kind9") == \
+        at(5) + "hints of an unknown kind (9) are not supported on this entry"
+    for hs in (2, 3):
+        d = std_dump(hand, hand.description(), inputs, hs)
+        assert refusal(builds, d, "set%d" % hs).startswith(
+            "hint_set must be ZKMI_HINTS_BASIC (0) or ZKMI_HINTS_STD (1): this entry has no other set")
+    # under ZKMI_HINTS_BASIC the kinds are refused by name, as ever
+    d = std_dump(hand, hand.description(), inputs, 0)
+    assert refusal(builds, d, "set0") == at(0) + "hints limbs (kind 3) are not supported on this entry"

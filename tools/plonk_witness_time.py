@@ -9,7 +9,11 @@ address circuit (BASELINE config 5: 231 270 gates, domain 2^18), batch 512.  Pri
 (zkmi_scs_solver_load) for every lane count 1 .. 64 and the automatic one -- the plan's records,
 steps and inversions, and the solve alone (zkmi_scs_solve_batch without the wires copied out) -- then
 one batch through zkmi_plonk_prove_scs with the automatic lane count; the records of the three
-entries must be identical.  Keys without commitments only.
+entries must be identical.  With --workload address-commit the solver is loaded with the std hint
+set (limbs, lookup multiplicities, commitment) at the automatic lane count alone and the batch goes
+through zkmi_plonk_prove_scs_ex beside zkmi_plonk_prove_ex and zkmi_plonk_prove_witness_ex; the
+solve alone is not timed there (zkmi_scs_solve_batch refuses a plan with commitment hints), so the
+leg gives the plan's figures, the whole prove and its difference to the wire-form entry.
 
 --workload address-commit: the same circuit with its bytes range-checked through api.Commit
 (circuits.AddressCircuitCommit), proved through zkmi_plonk_prove_ex / zkmi_plonk_prove_witness_ex;
@@ -148,23 +152,26 @@ def measure(batch, workload="address", entry=None):
                     all(x.tobytes() == y.tobytes() for x, y in zip(cm_w, cm_i))}
     ctx.host_free(wires)
     if entry == "scs":
-        if n_c:
-            raise SystemExit("--entry scs: the solver entries do not carry commitments")
+        hints = "std" if n_c else "basic"
         t = time.perf_counter()
-        desc = sc.solver_description()
-        leg = {"description_s": time.perf_counter() - t, "n_wires": int(desc["n_wires"]),
+        desc = sc.solver_description(hints)
+        leg = {"description_s": time.perf_counter() - t, "n_wires": int(desc["n_wires"]), "hint_set": hints,
                "n_hints": int(len(desc["hint_kind"])), "lanes": {}}
-        for lanes in (1, 2, 4, 8, 16, 32, 64, 0):
+        for lanes in ((0,) if n_c else (1, 2, 4, 8, 16, 32, 64, 0)):
             t = time.perf_counter()
-            h = wp.load_solver(lanes)
+            h = wp.load_solver(lanes, hints=hints)
             load_s = time.perf_counter() - t
-            info = ctx.scs_solver_info(h)
-            st_s, t_s = median_ms(lambda: ctx.scs_solve_batch(h, inp, batch))
-            assert not st_s.any()
-            leg["lanes"]["auto" if lanes == 0 else str(lanes)] = dict(info, load_s=load_s, solve=t_s)
-        (rec_s, st_s), t_p = median_ms(lambda: wp.prove_raw(blind, inputs=inp))
+            info = dict(ctx.scs_solver_info(h), load_s=load_s)
+            if not n_c:
+                st_s, info["solve"] = median_ms(lambda: ctx.scs_solve_batch(h, inp, batch))
+                assert not st_s.any()
+            leg["lanes"]["auto" if lanes == 0 else str(lanes)] = info
+        (rec_s, st_s, *cm_s), t_p = median_ms(lambda: wp.prove_raw(blind, inputs=inp, **extra))
         assert not st_s.any()
         assert rec_s.tobytes() == rec_i.tobytes() == rec_w.tobytes(), "the three entries disagree"
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(cm_s, cm_i)), "the commit records disagree"
+        if n_c:   # solve, boundary synchronisations and commitment step, less the wire transfer
+            leg["prove_minus_witness_ms"] = t_p["median_ms"] - t_w["median_ms"]
         leg["prove"] = t_p
         leg["records_identical"] = True
         out["scs"] = leg
