@@ -21,10 +21,7 @@
 #include "sha256.h"
 #include <atomic>
 #include <cstring>
-#include "ff29.h"
-#if defined(__HIP_DEVICE_COMPILE__)
-#include "ff29_asm.h"
-#endif
+#include "solve_common.h"
 
 using namespace zk;
 
@@ -72,33 +69,13 @@ namespace zk {
 
 #define LANE const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x
 
-// Products of the element-wise kernels on the 9 x 29-bit form (the single-accumulator asm chain of
-// ff29_asm.h: ~365 instructions with unpack and canonical pack, ~540 for ff.h's mul).  The chain
-// computes a b 2^-261 where ff.h's mul computes a b 2^-256, so exponents are tracked instead of
-// converting data: write im_e(x) = x 2^e mod r (gnark's image is e = 256); then
-//     fmulp(im_e1(x), im_e2(y)) = im_(e1 + e2 - 261)(x y),
-// sums need equal exponents, and every key-side operand is stored (plonk_pk_load) or every per-proof
-// scalar converted once (fmulp by the constant 2^(e' - e + 261)) with the exponent that makes the
-// result come out at 256 again.  Each kernel's comments carry the exponents.
-__device__ __forceinline__ Fr fmulp(const Fr& a, const Fr& b) {
-  Fr r;
-#if defined(__HIP_DEVICE_COMPILE__)
-  pack_canonical<Fr29Params>(r.v, mul_asm(unpack29<Fr29Params>(a.v), unpack29<Fr29Params>(b.v)));
-#else
-  r = a;   // device-only helper
-#endif
-  return r;
-}
-// 2^e mod r as a canonical integer, e >= 256: Fr::one() doubled e - 256 times (host)
-// x 2^k by doublings: im_e(x) -> im_(e + k)(x)
-__host__ __device__ static inline Fr lift(Fr x, int k) {
-  for (int i = 0; i < k; i++) x = add(x, x);
-  return x;
-}
+// Products of the element-wise kernels are fmulp on the 9 x 29-bit form; the exponent calculus the
+// kernels' comments use (im_e, lift) is written out with it in solve_common.h.
 __global__ void plonk_lift_kernel(Fr* x, size_t count, int k) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) x[i] = lift(x[i], k);
 }
+// 2^e mod r as a canonical integer, e >= 256: Fr::one() doubled e - 256 times (host)
 static Fr pow2_image(int e) {
   Fr x = Fr::one();
   for (int i = 256; i < e; i++) x = add(x, x);
@@ -416,12 +393,6 @@ struct ScsDev {
   uint32_t n_gates, n_public;
   const uint8_t* skip;
 };
-__device__ __forceinline__ Fr scs_term(uint32_t mark, const Fr& x, const Fr* q) {
-  if (mark == SCS_MARK_ZERO) return Fr::zero();
-  if (mark == SCS_MARK_ONE) return x;
-  if (mark == SCS_MARK_MINUS_ONE) return neg(x);
-  return fmulp(x, *q);
-}
 // COLS = false (zkmi_scs_solve_batch): the check alone, no column and no public-input stores.
 template <bool CM, bool COLS>
 __device__ __forceinline__ void scs_gate_rows(const ScsDev& s, const Fr* __restrict__ w,
@@ -440,10 +411,10 @@ __device__ __forceinline__ void scs_gate_rows(const ScsDev& s, const Fr* __restr
       bi_st(b, g, p, Bp, vb);
       bi_st(c, g, p, Bp, vc);
     }
-    Fr sum = add(add(scs_term(mk & 3, va, s.sel + g), scs_term((mk >> 2) & 3, vb, s.sel + ng + g)),
-                 scs_term((mk >> 4) & 3, vc, s.sel + 2 * ng + g));
+    Fr sum = add(add(sel_term(mk & 3, va, s.sel + g), sel_term((mk >> 2) & 3, vb, s.sel + ng + g)),
+                 sel_term((mk >> 4) & 3, vc, s.sel + 2 * ng + g));
     const uint32_t mm = (mk >> 6) & 3;
-    if (mm != SCS_MARK_ZERO) sum = add(sum, scs_term(mm, fmulp(va, lift(vb, 5)), s.sel + 3 * ng + g));
+    if (mm != SCS_MARK_ZERO) sum = add(sum, sel_term(mm, fmulp(va, lift(vb, 5)), s.sel + 3 * ng + g));
     if (((mk >> 8) & 3) != SCS_MARK_ZERO) sum = add(sum, s.sel[4 * ng + g]);
     if (g < s.n_public) {
       sum = sub(sum, va);

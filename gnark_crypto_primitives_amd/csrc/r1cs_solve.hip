@@ -21,8 +21,7 @@
 #include <vector>
 
 #include "zkmi_internal.h"
-#include "ff29.h"
-#include "ff29_asm.h"
+#include "solve_common.h"
 #include "r1cs_plan.h"
 
 using namespace zk;
@@ -43,13 +42,6 @@ struct zkmi_r1cs_solver {
 };
 
 namespace zk {
-
-// a b 2^-261 on the asm chain of ff29_asm.h (witness.hip: r1cs_eval_kernel forms its rows with it)
-__device__ __forceinline__ Fr fmul_261(const Fr& a, const Fr& b) {
-  Fr r;
-  pack_canonical<Fr29Params>(r.v, mul_asm(unpack29<Fr29Params>(a.v), unpack29<Fr29Params>(b.v)));
-  return r;
-}
 
 // sum over the S sub-lanes of a proof (lanes p, p + 64 / S, ...): every sub-lane ends with the total
 template <int S>
@@ -136,7 +128,7 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
       const Fr x2 = bi_ld(w, t2.x & R1CS_IDX_MASK, p, Bp);
       const Fr k2 = coeffs[t2.y & R1CS_IDX_MASK];
       if (row < mul_rows)   // wave-uniform
-        accumulate(t0.x >> 30, fmul_261(x0, k0));
+        accumulate(t0.x >> 30, fmulp(x0, k0));
       else
         accumulate(t0.x >> 30, (t0.y >> 30) == 2 ? neg(x0) : x0);
       tp += S;
@@ -187,11 +179,9 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
         // k queries, one per sub-lane; a query outside the table (coef = its size) counts nowhere
         const Fr v = from_mont(sa);
         if (sl < k && (v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0 &&
-            v.v[0] < par) {
-          uint32_t* cnt = reinterpret_cast<uint32_t*>(reinterpret_cast<uint4*>(w) +
-                                                      (size_t)outs[target + v.v[0]] * 2 * Bp + p);
-          __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+            v.v[0] < par)
+          __hip_atomic_fetch_add(lookup_counter(w, outs[target + v.v[0]], p, Bp), 1u, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
       } else if (kind != RK_COMMIT) {   // (a launch ends in front of a commitment)
         if (kind == RK_LIMBS) {
           // the sub-lanes split the k output wires
@@ -201,16 +191,14 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
         } else if (kind == RK_COUNT_BEGIN) {
           // the sub-lanes zero the k counters; the stores are complete before the first count
           for (uint32_t j = sl; j < k; j += S) bi_st(w, outs[target + j], p, Bp, Fr::zero());
-          __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+          stores_complete();
         } else {   // RK_COUNT_END: the counts are complete; integers into field images, in place
-          __builtin_amdgcn_s_waitcnt(0x0F70);
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+          stores_complete();
           for (uint32_t j = sl; j < k; j += S) {
             const uint32_t wire = outs[target + j];
-            uint32_t* cnt = reinterpret_cast<uint32_t*>(reinterpret_cast<uint4*>(w) + (size_t)wire * 2 * Bp + p);
             bi_st(w, wire, p, Bp,
-                  r1cs_small(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+                  r1cs_small(__hip_atomic_load(lookup_counter(w, wire, p, Bp), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT)));
           }
         }
         // the wire values fetched ahead may be among the wires stored: fetch them again behind the stores
@@ -236,7 +224,7 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
         if (kind == RK_ASSERT) {
           if (ab != sc) st = ZKMI_ERR_UNSATISFIED;
         } else {   // k x + c = a b; the completed c is a b
-          xs = fmul_261(sub(ab, sc), kinv);
+          xs = fmulp(sub(ab, sc), kinv);
           sc = ab;
         }
       } else {
@@ -248,7 +236,7 @@ __global__ __launch_bounds__(64) void r1cs_solve_kernel(const uint4* __restrict_
         } else {
           if (den.is_zero()) st = ZKMI_ERR_UNSATISFIED;
           const Fr q = mul(sc, inv);   // the completed factor
-          xs = fmul_261(sub(q, kind == RK_SOLVE_L ? sa : sb), kinv);
+          xs = fmulp(sub(q, kind == RK_SOLVE_L ? sa : sb), kinv);
           if (kind == RK_SOLVE_L)
             sa = q;
           else
@@ -306,20 +294,10 @@ static int r1cs_solve_range(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, Fr* w, Fr*
     return ZKMI_ERR_ARG;
   }
   if (begin == end) return ZKMI_OK;
-  decltype(&launch_r1cs_solve<1>) launch;
-  switch (s->S) {
-    case 1: launch = launch_r1cs_solve<1>; break;
-    case 2: launch = launch_r1cs_solve<2>; break;
-    case 4: launch = launch_r1cs_solve<4>; break;
-    case 8: launch = launch_r1cs_solve<8>; break;
-    case 16: launch = launch_r1cs_solve<16>; break;
-    case 32: launch = launch_r1cs_solve<32>; break;
-    case 64: launch = launch_r1cs_solve<64>; break;
-    default:
-      ctx->err = "r1cs solver: lanes_per_proof must be a power of two, 1 .. 64";
-      return ZKMI_ERR_ARG;
+  if (!with_lanes(s->S, [&](auto S) { launch_r1cs_solve<S>(ctx, s, w, a, b, c, status, Bp, begin, end); })) {
+    ctx->err = "r1cs solver: lanes_per_proof must be a power of two, 1 .. 64";
+    return ZKMI_ERR_ARG;
   }
-  launch(ctx, s, w, a, b, c, status, Bp, begin, end);
   ZK_HIP(hipGetLastError());
   return ZKMI_OK;
 }
@@ -330,28 +308,6 @@ static int r1cs_solve_bi(zkmi_ctx* ctx, const zkmi_r1cs_solver* s, Fr* w, Fr* a,
                          int32_t* status, size_t Bp) {
   int rc = r1cs_solve_init(ctx, w, status, Bp);
   return rc ? rc : r1cs_solve_range(ctx, s, w, a, b, c, status, Bp, 0, s->n_records);
-}
-
-// n elements of a caller array (host or device) into a host vector
-template <class T>
-static bool fetch(std::vector<T>& dst, const void* src, size_t n) {
-  dst.resize(n);
-  if (n == 0) return true;
-  if (!src || hipMemcpy(dst.data(), src, n * sizeof(T), hipMemcpyDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return true;
-}
-
-template <class T>
-static bool upload(T** dst, const void* src, size_t n) {
-  if (hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess ||
-      (n && hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return true;
 }
 
 static int solver_load(zkmi_ctx* ctx, const zkmi_r1cs* m, const zkmi_r1cs_solver_desc* d,

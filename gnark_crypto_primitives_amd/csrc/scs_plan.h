@@ -116,7 +116,7 @@ struct ScsPlan {
   std::vector<uint32_t> outs;       // output wires of the NBITS records
   std::vector<uint32_t> input_wire; // n_inputs
   // ZKMI_HINTS_STD
-  bool std_records = false;         // a record of a class from SK_LIMBS on: scs_std_kernel runs the plan
+  bool std_records = false;         // a record of a class from SK_LIMBS on: scs_solve_kernel<S, 1> runs the plan
   struct Commit {
     uint32_t instr, step, wire;     // the hint's instruction, the first step of its barrier level, its wire
     std::vector<uint32_t> wires;    // the committed wires, operand order
@@ -543,7 +543,7 @@ inline std::string scs_plan_build(const ScsPlanIn& in, ScsPlan* out, uint32_t ma
   return "";
 }
 
-// What a record computes, on the host (the device's twins are scs_solve_kernel and scs_std_kernel):
+// What a record computes, on the host (the device's twin is scs_solve_kernel, scs_solve.hip):
 // `ld(w)` reads a wire, `st(w, v)` stores one; returns false when the record divides by zero.  coefs:
 // the plan's table in gnark's image.  A lookup counter is the low word of its wire's row, as on the
 // device: COUNT_Q reads the row and stores it back with that word one higher.

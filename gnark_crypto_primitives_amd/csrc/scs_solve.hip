@@ -20,8 +20,7 @@
 #include <vector>
 
 #include "zkmi_internal.h"
-#include "ff29.h"
-#include "ff29_asm.h"
+#include "solve_common.h"
 #include "scs_plan.h"
 
 using namespace zk;
@@ -34,76 +33,72 @@ struct zkmi_scs_solver {
   Fr* coefs = nullptr;       // rows of six: qL qR qO qM as 2^261 images, qC and K in gnark's image
   uint32_t* outs = nullptr;
   uint32_t* input_wire = nullptr;
-  // ZKMI_HINTS_STD: a plan with records of the std classes runs scs_std_kernel (scs_solve_std.hip);
+  // ZKMI_HINTS_STD.  The EXT = 1 instance of scs_solve_kernel runs a plan with a record of the std
+  // classes, which only it can, and also every plan with commitment hints: such a plan is loaded under
+  // the std set and runs in pieces between its commitments, and those pieces have always run on the
+  // kernel with the step range.  EXT = 0 is thereby only ever launched over a whole plan.
+  bool ext = false;
   // the commitment hints, with the solver's device copy of their wire lists
-  bool std_records = false;
   std::vector<ScsPlan::Commit> commits;
   std::vector<uint32_t*> commit_wires;
 };
 
 namespace zk {
 
-// a b 2^-261 on the asm chain of ff29_asm.h (fmulp of plonk.hip, fmul_261 of r1cs_solve.hip)
-__device__ __forceinline__ Fr scs_fmulp(const Fr& a, const Fr& b) {
-  Fr r;
-  pack_canonical<Fr29Params>(r.v, mul_asm(unpack29<Fr29Params>(a.v), unpack29<Fr29Params>(b.v)));
-  return r;
-}
-// x 2^5: a 2^256 image as the 2^261 operand of scs_fmulp
-__device__ __forceinline__ Fr scs_lift5(Fr x) {
-#pragma unroll
-  for (int i = 0; i < 5; i++) x = add(x, x);
-  return x;
-}
-// selector times value by the selector's mark (scs_check.h); q is a 2^261 image
-__device__ __forceinline__ Fr scs_sel_term(uint32_t mark, const Fr& x, const Fr* q) {
-  if (mark == SCS_MARK_ZERO) return Fr::zero();
-  if (mark == SCS_MARK_ONE) return x;
-  if (mark == SCS_MARK_MINUS_ONE) return neg(x);
-  return scs_fmulp(x, *q);
-}
-
+// Steps [begin, end) of the plan, so that the caller can stop at a commitment's boundary, form the
+// commitment and go on.
 // One wavefront = 64 / S proofs x S sub-lanes, lane l = (sub-lane l / (64 / S), proof l % (64 / S)),
 // as in solve_vliw_kernel and r1cs_solve_kernel.  Steps are a wave-uniform loop; sub-lane s runs
 // record s of the step, one 32-byte load that the lanes of a sub-lane share; the step's class is the
 // same in all its records (read through readfirstlane), so the only divergence is between the marks
-// of the records and the padding.  Wire values are coalesced row segments of the batch-inner matrix.
+// of the records and the padding.  Wire values are coalesced row segments of the batch-inner matrix,
+// in gnark's 2^256 image; products are fmulp against 2^261 images.
 // A wire stored in one step is loaded in later steps by lanes of the same wavefront only, and a
 // wavefront's vector memory instructions reach the L1 / L2 in issue order (the argument at the top of
 // the VLIW solver in solve.hip): the wavefront-scope fence pins the compiler's order and costs no
 // instruction; there is no vmcnt(0) per step.  The plan guarantees that no record reads a wire its
-// own step writes.  The next step's record is fetched before this step's work; the records end in a
-// step of padding for that.
-// All counts and indices come from a plan that scs_plan_build has checked.
-template <int S>
+// own step writes.  The next step's record is fetched before this step's work; the records are
+// contiguous and end in a step of padding, so the fetch ahead of `end` stays inside the array.
+// EXT = 1: the plan may hold records of the classes SK_LIMBS .. SK_COUNT_END (ZKMI_HINTS_STD), named
+// in a record's fourth control word; plans without one run the EXT = 0 instance, which holds none of
+// their code and does not read that word.  The lookup counters are those of solve_common.h, as in
+// r1cs_solve.hip; zeroing, counting and reading back are three levels of the plan, so three
+// different steps.
+// Bits and limbs under a per-lane index come out of chains of selects, never an indexed register array.
+// All counts and indices come from a plan that scs_plan_build has checked: a wire index is below
+// n_wires, outs[target + j] exists for every j a record names, and a query counts only below its
+// table's size.
+template <int S, bool EXT>
 __global__ __launch_bounds__(64) void scs_solve_kernel(const uint4* __restrict__ recs,
                                                        const Fr* __restrict__ coefs,
                                                        const uint32_t* __restrict__ outs, Fr* w,
                                                        int32_t* __restrict__ status, size_t Bp,
-                                                       uint32_t n_steps) {
+                                                       uint32_t begin, uint32_t end) {
   constexpr int PPW = 64 / S;
   const uint32_t sl = threadIdx.x / PPW;
   const size_t p = (size_t)blockIdx.x * PPW + (threadIdx.x % PPW);
   int32_t st = 0;
-  const uint4* rp = recs + 2 * (size_t)sl;
+  const uint4* rp = recs + 2 * ((size_t)begin * S + sl);
   uint4 r0 = rp[0], r1 = rp[1];
-  for (uint32_t t = 0; t < n_steps; t++) {
+  for (uint32_t t = begin; t < end; t++) {
     const uint4 q0 = r0, q1 = r1;
     rp += 2 * S;
     r0 = rp[0];
     r1 = rp[1];
     const uint32_t ctl = q1.x;
-    const uint32_t cls = __builtin_amdgcn_readfirstlane(ctl >> SCS_CTL_CLASS) & 3;
+    const uint32_t xcls = EXT ? __builtin_amdgcn_readfirstlane(q1.w) : 0u;
+    const uint32_t cls = xcls ? xcls : __builtin_amdgcn_readfirstlane(ctl >> SCS_CTL_CLASS) & 3;
     const Fr* q = coefs + (size_t)q1.y * SCS_COEF_ROW;
     const bool store = ctl & SCS_CTL_STORE;
     Fr va = Fr::zero(), vb = Fr::zero(), vc = Fr::zero();
     if (ctl >> SCS_CTL_READ & 1) va = bi_ld(w, q0.x, p, Bp);
     if (ctl >> (SCS_CTL_READ + 1) & 1) vb = bi_ld(w, q0.y, p, Bp);
     if (ctl >> (SCS_CTL_READ + 2) & 1) vc = bi_ld(w, q0.z, p, Bp);
+    const Fr ta = sel_term(ctl & 3, va, q), tb = sel_term((ctl >> 2) & 3, vb, q + 1);
     // the known part of the gate (a hint: its input), in gnark's image: 256 + 261 - 261
-    Fr rest = add(add(scs_sel_term(ctl & 3, va, q), scs_sel_term((ctl >> 2) & 3, vb, q + 1)),
-                  scs_sel_term((ctl >> 4) & 3, vc, q + 2));
-    if (((ctl >> 8) & 3) != SCS_MARK_ZERO) rest = add(rest, q[4]);
+    Fr rest = add(add(ta, tb), sel_term((ctl >> 4) & 3, vc, q + 2));
+    const bool has_c = ((ctl >> 8) & 3) != SCS_MARK_ZERO;
+    if (has_c) rest = add(rest, q[4]);
     const uint32_t mm = (ctl >> 6) & 3, mk = (ctl >> SCS_CTL_MARK_K) & 3;
     if (cls == SK_NBITS) {
       const Fr v = from_mont(rest);
@@ -118,22 +113,52 @@ __global__ __launch_bounds__(64) void scs_solve_kernel(const uint4* __restrict__
         const uint32_t bit = (word >> (at & 31)) & 1u;
         bi_st(w, outs[q0.w + j], p, Bp, bit ? Fr::one() : Fr::zero());
       }
+    } else if (EXT && cls == SK_LIMBS) {
+      const Fr v = from_mont(rest);
+      const uint32_t j0 = q1.z & 0xffffu, cnt = store ? (q1.z >> 16) & 0xffu : 0u, width = q1.z >> 24;
+      for (uint32_t j = 0; j < cnt; j++)
+        bi_st(w, outs[q0.w + j], p, Bp, r1cs_small(std_limb(v, (j0 + j) * width, width)));
+    } else if (EXT && cls == SK_BYTEOP) {
+      // the two terms on their own: a constant one sits in qC (a) or K (b)
+      const uint32_t u = from_mont(has_c ? add(ta, q[4]) : ta).v[0];
+      const uint32_t v = from_mont(mk != SCS_MARK_ZERO ? add(tb, q[5]) : tb).v[0];
+      if (store) bi_st(w, q0.w, p, Bp, r1cs_small(q1.z == 1 ? u ^ v : u & v));
+    } else if (EXT && cls == SK_COUNT_ZERO) {
+      const uint32_t cnt = store ? q1.z >> 16 : 0u;
+      for (uint32_t j = 0; j < cnt; j++) bi_st(w, outs[q0.w + j], p, Bp, Fr::zero());
+      stores_complete();   // the zeroes, before the first count
+    } else if (EXT && cls == SK_COUNT_Q) {
+      // a query outside the table counts nowhere
+      const Fr v = from_mont(rest);
+      if (store && (v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0 && v.v[0] < q1.z)
+        __hip_atomic_fetch_add(lookup_counter(w, outs[q0.w + v.v[0]], p, Bp), 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    } else if (EXT && cls == SK_COUNT_END) {
+      // the counts are complete; integers into field images, in place
+      stores_complete();
+      const uint32_t cnt = store ? q1.z >> 16 : 0u;
+      for (uint32_t j = 0; j < cnt; j++) {
+        const uint32_t wire = outs[q0.w + j];
+        bi_st(w, wire, p, Bp,
+              r1cs_small(__hip_atomic_load(lookup_counter(w, wire, p, Bp), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT)));
+      }
     } else {
       Fr x;
       if (cls == SK_LIN) {
         // x = K rest, K = -1 / k
-        if (mm != SCS_MARK_ZERO) rest = add(rest, scs_sel_term(mm, scs_fmulp(va, scs_lift5(vb)), q + 3));
-        x = mk == SCS_MARK_ONE ? rest : mk == SCS_MARK_MINUS_ONE ? neg(rest) : scs_fmulp(rest, scs_lift5(q[5]));
+        if (mm != SCS_MARK_ZERO) rest = add(rest, sel_term(mm, fmulp(va, lift<5>(vb)), q + 3));
+        x = mk == SCS_MARK_ONE ? rest : mk == SCS_MARK_MINUS_ONE ? neg(rest) : fmulp(rest, lift<5>(q[5]));
       } else {
         // DIV: x = -rest / (k + qM other); INVZERO: x = 1 / rest, 0 for 0 (the inverse of 0 is 0)
         Fr den = rest;
         if (cls == SK_DIV) {
-          den = scs_sel_term(mm, ctl & SCS_CTL_OTHER_A ? va : vb, q + 3);
+          den = sel_term(mm, ctl & SCS_CTL_OTHER_A ? va : vb, q + 3);
           if (mk != SCS_MARK_ZERO) den = add(den, q[5]);
           if (store && den.is_zero()) st = ZKMI_ERR_UNSATISFIED;
         }
         const Fr inv = inverse(den);
-        x = cls == SK_DIV ? neg(scs_fmulp(rest, scs_lift5(inv))) : inv;
+        x = cls == SK_DIV ? neg(fmulp(rest, lift<5>(inv))) : inv;
       }
       if (store) bi_st(w, q0.w, p, Bp, x);
     }
@@ -153,9 +178,11 @@ __global__ void scs_solve_init_kernel(const Fr* __restrict__ in, const uint32_t*
 }
 
 template <int S>
-static void launch_scs_solve(zkmi_ctx* ctx, const zkmi_scs_solver* s, Fr* w, int32_t* status, size_t Bp) {
-  hipLaunchKernelGGL(scs_solve_kernel<S>, dim3((unsigned)(Bp * S / 64)), dim3(64), 0, ctx->stream,
-                     s->records, s->coefs, s->outs, w, status, Bp, s->n_steps);
+static void launch_scs_solve(zkmi_ctx* ctx, const zkmi_scs_solver* s, Fr* w, int32_t* status, size_t Bp,
+                             uint32_t begin, uint32_t end) {
+  const auto kernel = s->ext ? scs_solve_kernel<S, true> : scs_solve_kernel<S, false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(Bp * S / 64)), dim3(64), 0, ctx->stream, s->records, s->coefs,
+                     s->outs, w, status, Bp, begin, end);
 }
 
 const zkmi_scs* scs_solver_system(const zkmi_scs_solver* s) { return s->sys; }
@@ -178,11 +205,12 @@ int scs_solver_stage(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs
   }
   return ZKMI_OK;
 }
-// steps [begin, end) of a plan under ZKMI_HINTS_STD, between the boundaries of its commitments
+// steps [begin, end) of the plan: all of it, or the piece between two boundaries of its commitments
 int scs_solver_run_steps(zkmi_ctx* ctx, const zkmi_scs_solver* s, Fr* w, int32_t* status, size_t Bp,
                          uint32_t begin, uint32_t end) {
-  if (begin > end || end > s->n_steps ||
-      !scs_std_launch(ctx->stream, s->S, s->records, s->coefs, s->outs, w, status, Bp, begin, end)) {
+  if (begin > end || end > s->n_steps || !with_lanes(s->S, [&](auto S) {
+        if (begin < end) launch_scs_solve<S>(ctx, s, w, status, Bp, begin, end);
+      })) {
     ctx->err = "scs solver: a step range outside the plan, or lanes_per_proof is no power of two, 1 .. 64";
     return ZKMI_ERR_ARG;
   }
@@ -192,45 +220,8 @@ int scs_solver_run_steps(zkmi_ctx* ctx, const zkmi_scs_solver* s, Fr* w, int32_t
 
 int scs_solver_run(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs, size_t batch, size_t Bp,
                    Fr* staged, Fr* w, int32_t* status) {
-  int rc;
-  if ((rc = scs_solver_stage(ctx, s, inputs, batch, Bp, staged, w))) return rc;
-  if (s->std_records) return scs_solver_run_steps(ctx, s, w, status, Bp, 0, s->n_steps);
-  decltype(&launch_scs_solve<1>) launch;
-  switch (s->S) {
-    case 1: launch = launch_scs_solve<1>; break;
-    case 2: launch = launch_scs_solve<2>; break;
-    case 4: launch = launch_scs_solve<4>; break;
-    case 8: launch = launch_scs_solve<8>; break;
-    case 16: launch = launch_scs_solve<16>; break;
-    case 32: launch = launch_scs_solve<32>; break;
-    case 64: launch = launch_scs_solve<64>; break;
-    default:
-      ctx->err = "scs solver: lanes_per_proof must be a power of two, 1 .. 64";
-      return ZKMI_ERR_ARG;
-  }
-  if (s->n_steps) launch(ctx, s, w, status, Bp);
-  ZK_HIP(hipGetLastError());
-  return ZKMI_OK;
-}
-
-template <class T>
-static bool fetch(std::vector<T>& dst, const void* src, size_t n) {
-  dst.resize(n);
-  if (n == 0) return true;
-  if (!src || hipMemcpy(dst.data(), src, n * sizeof(T), hipMemcpyDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return true;
-}
-template <class T>
-static bool upload(T** dst, const void* src, size_t n) {
-  if (hipMalloc((void**)dst, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess ||
-      (n && hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyDefault) != hipSuccess)) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return true;
+  const int rc = scs_solver_stage(ctx, s, inputs, batch, Bp, staged, w);
+  return rc ? rc : scs_solver_run_steps(ctx, s, w, status, Bp, 0, s->n_steps);
 }
 
 static int solver_load(zkmi_ctx* ctx, const zkmi_scs* m, const zkmi_scs_solver_desc* d, zkmi_scs_solver** out) {
@@ -312,8 +303,8 @@ static int solver_load(zkmi_ctx* ctx, const zkmi_scs* m, const zkmi_scs_solver_d
     s->sys->hx[c] = m->hx[c];
     ok = upload(&s->sys->x[c], m->x[c], ng);
   }
-  s->std_records = plan.std_records;
   s->commits = plan.commits;
+  s->ext = plan.std_records || !s->commits.empty();
   for (size_t i = 0; ok && i < s->commits.size(); i++) {
     s->commit_wires.push_back(nullptr);
     ok = upload(&s->commit_wires.back(), s->commits[i].wires.data(), s->commits[i].wires.size());

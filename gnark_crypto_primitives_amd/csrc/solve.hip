@@ -617,20 +617,12 @@ static void launch_solve(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr*
 int solve_rows(zkmi_ctx* ctx, const zkmi_cs* cs, Fr* slots, Fr* a, Fr* b, Fr* c, int32_t* status,
                size_t Bp, uint32_t row_begin, uint32_t row_end) {
   if (row_begin >= row_end) return ZKMI_OK;
-  decltype(&launch_solve<1>) launch;
-  switch (cs->lanes_per_proof) {
-    case 1: launch = launch_solve<1>; break;
-    case 2: launch = launch_solve<2>; break;
-    case 4: launch = launch_solve<4>; break;
-    case 8: launch = launch_solve<8>; break;
-    case 16: launch = launch_solve<16>; break;
-    case 32: launch = launch_solve<32>; break;
-    case 64: launch = launch_solve<64>; break;
-    default:
-      ctx->err = "cs: lanes_per_proof must be a power of two, 1 .. 64";
-      return ZKMI_ERR_ARG;
+  if (!with_lanes(cs->lanes_per_proof, [&](auto S) {
+        launch_solve<S>(ctx, cs, slots, a, b, c, status, Bp, row_begin, row_end);
+      })) {
+    ctx->err = "cs: lanes_per_proof must be a power of two, 1 .. 64";
+    return ZKMI_ERR_ARG;
   }
-  launch(ctx, cs, slots, a, b, c, status, Bp, row_begin, row_end);
   ZK_HIP(hipGetLastError());
   return ZKMI_OK;
 }

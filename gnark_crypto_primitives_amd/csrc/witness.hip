@@ -18,10 +18,7 @@
 #include <thread>
 
 #include "zkmi_internal.h"
-#include "ff29.h"
-#if defined(__HIP_DEVICE_COMPILE__)
-#include "ff29_asm.h"
-#endif
+#include "solve_common.h"
 
 using namespace zk;
 
@@ -183,18 +180,9 @@ struct R1csDev {
   const Fr* coeffs;
   uint32_t n_constraints;
 };
-// a b 2^-261 on the 9 x 29-bit form (the asm chain of ff29_asm.h, ~365 instructions against ~540 of
-// ff.h's mul): with the coefficients stored as 2^261 images (zkmi_r1cs_load lifts them by 2^5) a
-// wire in gnark's 2^256 image times a coefficient comes out in the 2^256 image again
-__device__ __forceinline__ Fr fmul_261(const Fr& a, const Fr& b) {
-  Fr r;
-#if defined(__HIP_DEVICE_COMPILE__)
-  pack_canonical<Fr29Params>(r.v, mul_asm(unpack29<Fr29Params>(a.v), unpack29<Fr29Params>(b.v)));
-#else
-  r = a;   // device-only helper
-#endif
-  return r;
-}
+// Products are fmulp (solve_common.h): with the coefficients stored as 2^261 images (zkmi_r1cs_load
+// lifts them by 2^5) a wire in gnark's 2^256 image times a coefficient comes out in the 2^256 image
+// again
 __global__ __launch_bounds__(256) void r1cs_eval_kernel(R1csDev m, const Fr* __restrict__ w,
                                                         Fr* __restrict__ a, Fr* __restrict__ b,
                                                         Fr* __restrict__ c, int32_t* __restrict__ st,
@@ -217,7 +205,7 @@ __global__ __launch_bounds__(256) void r1cs_eval_kernel(R1csDev m, const Fr* __r
       else if (kind == 2)
         sum = sub(sum, x);
       else
-        sum = add(sum, fmul_261(x, m.coeffs[tm.y & 0x3fffffffu]));
+        sum = add(sum, fmulp(x, m.coeffs[tm.y & 0x3fffffffu]));
     }
     acc[s] = sum;
   }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -223,7 +224,7 @@ struct zkmi_r1cs {
   uint32_t* ptr[3] = {};   // device, n_constraints + 1 offsets each (L, R, O)
   uint2* terms[3] = {};    // device, x = wire, y = coefficient index | kind << 30
   size_t nnz[3] = {};
-  zk::Fr* coeffs = nullptr;   // device, 2^261 images (gnark's Montgomery image times 2^5: fmul_261)
+  zk::Fr* coeffs = nullptr;   // device, 2^261 images (gnark's Montgomery image times 2^5: fmulp)
 };
 
 // the sparse constraint system of zkmi_scs_load (plonk.hip; checks: scs_check.h)
@@ -311,9 +312,45 @@ int scs_solver_stage(zkmi_ctx* ctx, const zkmi_scs_solver* s, const void* inputs
                      Fr* staged, Fr* w);
 int scs_solver_run_steps(zkmi_ctx* ctx, const zkmi_scs_solver* s, Fr* w, int32_t* status, size_t Bp,
                          uint32_t begin, uint32_t end);
-// scs_solve_std.hip: steps [begin, end) of a plan on scs_std_kernel<S>; false: S is no lane count
-bool scs_std_launch(hipStream_t stream, uint32_t S, const uint4* recs, const Fr* coefs, const uint32_t* outs,
-                    Fr* w, int32_t* status, size_t Bp, uint32_t begin, uint32_t end);
+
+// The loaders of the two gnark-shaped solvers (r1cs_solve.hip, scs_solve.hip): n elements of a caller
+// array (host or device) into a host vector, and into device memory of their own; false: the copy or
+// the allocation failed (the sticky error is cleared)
+template <class T>
+static bool fetch(std::vector<T>& dst, const void* src, size_t n) {
+  dst.resize(n);
+  if (n == 0) return true;
+  if (!src || hipMemcpy(dst.data(), src, n * sizeof(T), hipMemcpyDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
+}
+template <class T>
+static bool upload(T** dst, const void* src, size_t n) {
+  if (hipMalloc((void**)dst, (n ? n : 1) * sizeof(T)) != hipSuccess ||
+      (n && hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyDefault) != hipSuccess)) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
+}
+
+// The solvers' kernels are templates in the number of lanes per proof: f(std::integral_constant<int, S>())
+// for S in {1, 2, 4, 8, 16, 32, 64}; false, and f not called, for any other S
+template <class F>
+static bool with_lanes(uint32_t S, F&& f) {
+  switch (S) {
+    case 1: f(std::integral_constant<int, 1>()); return true;
+    case 2: f(std::integral_constant<int, 2>()); return true;
+    case 4: f(std::integral_constant<int, 4>()); return true;
+    case 8: f(std::integral_constant<int, 8>()); return true;
+    case 16: f(std::integral_constant<int, 16>()); return true;
+    case 32: f(std::integral_constant<int, 32>()); return true;
+    case 64: f(std::integral_constant<int, 64>()); return true;
+    default: return false;
+  }
+}
 
 // RAII staging of a caller buffer (host or device) as device memory
 struct Staged {

@@ -42,7 +42,7 @@ static void put(FILE* f, const void* p, size_t words) {
 static void put_u32(FILE* f, uint32_t x) { put(f, &x, 1); }
 
 // a b 2^-261 as the device forms it: the Montgomery product (. 2^-256) times 2^-5
-static Fr fmul_261(const Fr& a, const Fr& b) {
+static Fr fmulp(const Fr& a, const Fr& b) {
   Fr k = Fr::zero();
   k.v[7] = 1u << 27;   // 2^251: the Montgomery image of 2^-5
   return mul(mul(a, b), k);
@@ -54,7 +54,7 @@ static Fr column(const R1csPlan& P, const R1csRecord& r, uint32_t sl, const std:
   for (uint32_t row = 0; row < r.mul_rows; row++) {
     const R1csTerm tm = P.terms[r.first + (size_t)row * P.S + sl];
     if (tm.wire >> 30 == RT_PAD) continue;
-    q = add(q, fmul_261(w[tm.wire & R1CS_IDX_MASK], P.coeffs[tm.coef & R1CS_IDX_MASK]));
+    q = add(q, fmulp(w[tm.wire & R1CS_IDX_MASK], P.coeffs[tm.coef & R1CS_IDX_MASK]));
   }
   return q;
 }
@@ -103,7 +103,7 @@ static int interpret(const R1csPlan& P, uint32_t n_inputs, const Fr* inputs, con
       if (tag == RT_PAD) continue;
       const Fr x = w[tm.wire & R1CS_IDX_MASK];
       const bool product = t < (size_t)r.mul_rows * P.S;
-      const Fr v = product ? fmul_261(x, P.coeffs[tm.coef & R1CS_IDX_MASK]) : unit == 2 ? neg(x) : x;
+      const Fr v = product ? fmulp(x, P.coeffs[tm.coef & R1CS_IDX_MASK]) : unit == 2 ? neg(x) : x;
       s[tag] = add(s[tag], v);
     }
     const Fr kinv = P.coeffs[r.coef_inv];
@@ -144,7 +144,7 @@ static int interpret(const R1csPlan& P, uint32_t n_inputs, const Fr* inputs, con
         break;
       case RK_SOLVE_O: {
         const Fr ab = mul(s[0], s[1]);
-        x = fmul_261(sub(ab, s[2]), kinv);
+        x = fmulp(sub(ab, s[2]), kinv);
         s[2] = ab;
         break;
       }
@@ -152,7 +152,7 @@ static int interpret(const R1csPlan& P, uint32_t n_inputs, const Fr* inputs, con
         const int mine = r.kind == RK_SOLVE_L ? 0 : 1, other = 1 - mine;
         if (s[other].is_zero()) st = ZKMI_ERR_UNSATISFIED;
         const Fr q = mul(s[2], inverse(s[other]));
-        x = fmul_261(sub(q, s[mine]), kinv);
+        x = fmulp(sub(q, s[mine]), kinv);
         s[mine] = q;
       }
     }

@@ -46,7 +46,7 @@ static void put(FILE* f, const void* p, size_t words) {
 static void put_u32(FILE* f, uint32_t x) { put(f, &x, 1); }
 
 // a b 2^-261 as the device forms it: the Montgomery product (. 2^-256) times 2^-5
-static Fr fmul_261(const Fr& a, const Fr& b) {
+static Fr fmulp(const Fr& a, const Fr& b) {
   Fr k = Fr::zero();
   k.v[7] = 1u << 27;   // 2^251: the Montgomery image of 2^-5
   return mul(mul(a, b), k);
@@ -67,7 +67,7 @@ static int interpret(const R1csPlan& P, uint32_t n_inputs, const Fr* inputs, con
         for (uint32_t row = 0; row < r.mul_rows; row++) {
           const R1csTerm tm = P.terms[r.first + (size_t)row * P.S + sl];
           if (tm.wire >> 30 == RT_PAD) continue;
-          q = add(q, fmul_261(w[tm.wire & R1CS_IDX_MASK], P.coeffs[tm.coef & R1CS_IDX_MASK]));
+          q = add(q, fmulp(w[tm.wire & R1CS_IDX_MASK], P.coeffs[tm.coef & R1CS_IDX_MASK]));
         }
         const Fr v = from_mont(q);
         if ((v.v[1] | v.v[2] | v.v[3] | v.v[4] | v.v[5] | v.v[6] | v.v[7]) == 0 && v.v[0] < r.coef)
@@ -83,7 +83,7 @@ static int interpret(const R1csPlan& P, uint32_t n_inputs, const Fr* inputs, con
       if (tag == RT_PAD) continue;
       const Fr x = w[tm.wire & R1CS_IDX_MASK];
       const bool product = t < (size_t)r.mul_rows * P.S;
-      const Fr v = product ? fmul_261(x, P.coeffs[tm.coef & R1CS_IDX_MASK]) : unit == 2 ? neg(x) : x;
+      const Fr v = product ? fmulp(x, P.coeffs[tm.coef & R1CS_IDX_MASK]) : unit == 2 ? neg(x) : x;
       s[tag] = add(s[tag], v);
     }
     const Fr kinv = P.coeffs[r.coef_inv];
@@ -124,7 +124,7 @@ static int interpret(const R1csPlan& P, uint32_t n_inputs, const Fr* inputs, con
         break;
       case RK_SOLVE_O: {
         const Fr ab = mul(s[0], s[1]);
-        x = fmul_261(sub(ab, s[2]), kinv);
+        x = fmulp(sub(ab, s[2]), kinv);
         s[2] = ab;
         break;
       }
@@ -132,7 +132,7 @@ static int interpret(const R1csPlan& P, uint32_t n_inputs, const Fr* inputs, con
         const int mine = r.kind == RK_SOLVE_L ? 0 : 1, other = 1 - mine;
         if (s[other].is_zero()) st = ZKMI_ERR_UNSATISFIED;
         const Fr q = mul(s[2], inverse(s[other]));
-        x = fmul_261(sub(q, s[mine]), kinv);
+        x = fmulp(sub(q, s[mine]), kinv);
         s[mine] = q;
       }
     }

@@ -1,4 +1,4 @@
-"""The gnark-shaped PLONK solver under ZKMI_HINTS_STD on the GPU (scs_std_kernel<S>,
+"""The gnark-shaped PLONK solver under ZKMI_HINTS_STD on the GPU (scs_solve_kernel<S, 1>,
 zkmi_plonk_prove_scs_ex): the hand description of tests/test_native_scs_std_plan.py through
 zkmi_scs_solve_batch at every lane count against the Python reference; circuits with range checks,
 lookups and api.Commit proved from inputs alone, byte for byte against the prover that runs the
