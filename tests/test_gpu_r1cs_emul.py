@@ -14,8 +14,8 @@ from gnark_crypto_primitives_amd.frontend import compile_circuit
 from gnark_crypto_primitives_amd.frontend.compile import to_mont_array
 from gnark_crypto_primitives_amd.std import emulated as em
 from tests import helpers as H
+from tests.r1cs_plan_harness import NO_KEYS, EmulDirect, emul_direct_assignments
 from tests.test_emulated import ArithCircuit, FormatCircuit, format_assignment
-from tests.test_native_r1cs_emul import NO_KEYS, EmulDirect, emul_direct_assignments
 
 pytestmark = pytest.mark.gpu
 

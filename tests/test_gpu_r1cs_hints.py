@@ -14,8 +14,8 @@ from gnark_crypto_primitives_amd import groth16, lib, verify
 from gnark_crypto_primitives_amd.frontend import compile_circuit
 from gnark_crypto_primitives_amd.frontend.compile import Public, Secret, to_mont_array
 from tests import helpers as H
+from tests.r1cs_plan_harness import HintsPlain, hints_plain_assignments, limbs_of
 from tests.test_commitment import RangeCircuit, TwoCommitments
-from tests.test_native_r1cs_hints import HintsPlain, hints_plain_assignments, limbs_of
 
 pytestmark = pytest.mark.gpu
 

@@ -15,8 +15,8 @@ from gnark_crypto_primitives_amd import lib, plonk
 from gnark_crypto_primitives_amd.frontend import Public, Secret
 from gnark_crypto_primitives_amd.frontend.compile import to_mont_array
 from gnark_crypto_primitives_amd.frontend.scs import compile_scs
+from tests.scs_plan_harness import HandStd, std_inputs
 from tests.test_gpu_plonk_commit import RANGE_BAD, RANGE_GOOD, SEED, UNSAT, key, mont
-from tests.test_native_scs_std_plan import HandStd, std_inputs
 
 pytestmark = pytest.mark.gpu
 R = plonk.R

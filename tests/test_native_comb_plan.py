@@ -2,13 +2,11 @@
 tests/native/comb_plan_check.cpp prints the equal-k plan and the searched plan of one input through
 the functions zkmi_pk_load calls; built plain and with -fsanitize=address,undefined, the two builds
 must print the same.  Bytes and costs are recomputed here in Python."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import native_build
+
+pytestmark = native_build.needs_gxx
 ARBO = (40196, 27059, 40522, 65536, 27059)      # A, B1, K, Z (folded key), B2 of the Arbo-160 key
 GUARD = 0.02
 
@@ -27,28 +25,14 @@ def _cost(n, k, sg, phi):
 
 @pytest.fixture(scope="module")
 def exes(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("comb_plan")
-    out = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(d / ("comb_plan_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "comb_plan_check.cpp"),
-                               "-o", exe])
-        out.append(exe)
-    return out
+    return native_build.build("comb_plan_check.cpp", tmp_path_factory.mktemp("comb_plan"))
 
 
 def _plan(exes, n, budget, allow_signed=1, phi=0.5, guard=GUARD):
     args = [*map(str, n), repr(float(budget)), str(allow_signed), repr(phi), repr(guard)]
-    outs = [subprocess.check_output([e, *args], text=True) for e in exes]
-    assert outs[0] == outs[1], "the plain and the sanitized build disagree"
+    _, out, _ = native_build.run_both(exes, args)
     res = {}
-    for line in outs[0].splitlines():
+    for line in out.splitlines():
         name, *f = line.split()
         k, sg = [int(x) for x in f[:5]], [int(x) for x in f[5:10]]
         res[name] = {"k": k, "sg": sg, "fits": int(f[10]), "bytes": float(f[11]),

@@ -4,16 +4,11 @@ kernel calls, the signs C_0 .. C_253 and the parity e of edge and random scalars
 -fsanitize=address,undefined, the two builds must print the same.  Checked here in Python integers:
 sum_j (2 C_j - 1) 2^j = t | 1, e = 1 - (t & 1), and the constants that carry a scalar from one
 Montgomery image to the other."""
-import os
 import random
-import shutil
-import subprocess
-
-import pytest
 
 from tests import helpers as H
+from tests import native_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = H.R
 
 
@@ -24,21 +19,12 @@ def _values():
     return edge + [rng.randrange(R) for _ in range(40)]
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@native_build.needs_gxx
 def test_comb_sign_native(tmp_path):
     vals = _values()
-    outs = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(tmp_path / ("comb_sign_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "comb_sign_check.cpp"),
-                               "-o", exe])
-        outs.append(subprocess.check_output([exe, *["%064x" % v for v in vals]], text=True))
-    assert outs[0] == outs[1], "the plain and the sanitized build disagree"
-    lines = outs[0].splitlines()
+    _, out, _ = native_build.run_both(native_build.build("comb_sign_check.cpp", tmp_path),
+                                      ["%064x" % v for v in vals])
+    lines = out.splitlines()
     assert lines[0] == "ok map"
     assert len(lines) == 1 + len(vals) + 2
     for t, line in zip(vals, lines[1:]):

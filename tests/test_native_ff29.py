@@ -1,25 +1,21 @@
 """Host build of the GPU field/curve headers: the 9 x 29-bit lazy representation used by the MSM
 kernels (csrc/ff29.h, ec29.h) against the reference representation (csrc/ff.h, ec.h)."""
 import os
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import native_build
+
+ROOT = native_build.ROOT
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@native_build.needs_gxx
 def test_ff29_host_unit_tests(tmp_path):
-    exe = str(tmp_path / "test_ff29")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I",
-                           os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "native", "test_ff29.cpp"), "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "ff29 tests ok" in out.stdout
+    exes = native_build.build("test_ff29.cpp", tmp_path, kinds=("plain",))
+    assert "ff29 tests ok" in native_build.run_both(exes, timeout=300)[1]
 
 
 @pytest.fixture(scope="module")
@@ -28,15 +24,11 @@ def ff29_host_results(tmp_path_factory):
     operand sets of tests/ff29_ref.py: [(field, op, class, expected, got)]"""
     from tests import ff29_ref
     tmp = tmp_path_factory.mktemp("ff29_ops")
-    exe, operands = str(tmp / "ff29_ops"), str(tmp / "operands.bin")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=undefined,address",
-                           "-fno-sanitize-recover=all", "-I",
-                           os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "native", "ff29_ops.cpp"), "-o", exe])
+    operands = str(tmp / "operands.bin")
+    exes = native_build.build("ff29_ops.cpp", tmp, kinds=("sanitized",))
     recs = ff29_ref.write_operand_file(operands)
-    out = subprocess.run([exe, operands], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-4000:]
-    got = np.array(out.stdout.split(), dtype=np.int64).reshape(-1, 9)
+    out = native_build.run_both(exes, [operands], timeout=300)[1]
+    got = np.array(out.split(), dtype=np.int64).reshape(-1, 9)
     assert len(got) == sum(len(exp) for _, _, _, exp in recs)
     got = got.astype(np.uint32).view(np.int32)
     res, at = [], 0
@@ -46,7 +38,7 @@ def ff29_host_results(tmp_path_factory):
     return res
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@native_build.needs_gxx
 @pytest.mark.parametrize("field", [0, 1], ids=["fr", "fq"])
 def test_ff29_host_forms_match_bigint(ff29_host_results, field):
     """The C++ forms (mul, mul_ilp, sqr, mul_add2, wred, pack_canonical) on the host, limb for limb

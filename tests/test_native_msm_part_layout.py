@@ -5,13 +5,12 @@ the one that already prepares the next MSM.  tests/native/msm_part_layout_check.
 regions through the function msm_impl.h uses; built plain and with -fsanitize=address,undefined,
 the two builds must print the same.  Order, disjointness and alignment are checked here."""
 import itertools
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import native_build
+
+pytestmark = native_build.needs_gxx
 REGIONS = ["partial", "mid", "wsum", "usum", "counts", "d0", "ulist"]
 ELEMS = (128, 256)                  # one G1 / G2 accumulator
 CHUNKS = (1, 16)
@@ -23,28 +22,14 @@ GROUPS = (1, 10, 3450)
 
 @pytest.fixture(scope="module")
 def exes(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("msm_part_layout")
-    out = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(d / ("msm_part_layout_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "msm_part_layout_check.cpp"),
-                               "-o", exe])
-        out.append(exe)
-    return out
+    return native_build.build("msm_part_layout_check.cpp", tmp_path_factory.mktemp("msm_part_layout"))
 
 
 def _layouts(exes, configs):
     args = [str(x) for c in configs for x in c]
-    outs = [subprocess.check_output([e, *args], text=True) for e in exes]
-    assert outs[0] == outs[1], "the plain and the sanitized build disagree"
+    _, out, _ = native_build.run_both(exes, args)
     res = {}
-    for line in outs[0].splitlines():
+    for line in out.splitlines():
         f = line.split()
         cfg = tuple(int(x) for x in f[:7])
         entry = res.setdefault(cfg, {"regions": [], "bytes": None})

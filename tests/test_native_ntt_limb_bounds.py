@@ -1,31 +1,21 @@
 """The limb form the 29-bit transform chains keep between their passes (csrc/ntt.hip): the schedule
 run on the host build of csrc/ff29.h by tests/native/ntt_limb_bounds_check.cpp, a program of its
 own, built plain and with -fsanitize=address,undefined.  No GPU."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import native_build
+
+pytestmark = native_build.needs_gxx
 
 
 @pytest.fixture(scope="module")
 def exes(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("ntt_limb_bounds")
-    out = {}
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O2", "-g", "-fsanitize=address,undefined",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(d / ("ntt_limb_bounds_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "ntt_limb_bounds_check.cpp"),
-                               "-o", exe])
-        out[name] = exe
-    return out
+    # the sanitized build at -O2 too, for its run time alone: the schedule takes a third longer at -O1
+    plain, sanitized = native_build.build("ntt_limb_bounds_check.cpp", tmp_path_factory.mktemp("ntt_limb_bounds"),
+                                          sanitized_opt="-O2")
+    return {"plain": plain, "sanitized": sanitized}
 
 
 @pytest.mark.parametrize("build", ["plain", "sanitized"])

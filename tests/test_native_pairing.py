@@ -2,35 +2,23 @@
 Groth16 decision (decode and point checks, shared-squaring Miller loop, final exponentiation),
 against verify.py's Python integers.  The driver is built twice, plain -O2 and under UBSan + ASan (a
 program of its own, run directly), and both builds must print the same."""
-import os
 import random
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from gnark_crypto_primitives_amd import verify as V
-from tests import helpers, verify_vectors as vv
+from tests import helpers, native_build, verify_vectors as vv
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P, R = V.P, V.R
 PAIRS = [(5, 7), (0x1234567890abcdef1234567890abcdef, R - 3), (R - 1, 2 ** 200 + 9)]
 N_INPUTS = 3
 
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+pytestmark = native_build.needs_gxx
 
 
 def _hex(a):
     return np.ascontiguousarray(a, dtype=np.uint64).tobytes().hex()
-
-
-def _build(tmp, name, flags):
-    exe = str(tmp / name)
-    subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                           os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "native", "test_pairing.cpp"), "-o", exe])
-    return exe
 
 
 @pytest.fixture(scope="module")
@@ -77,19 +65,10 @@ def run(tmp_path_factory):
                " ".join(["vk", "0", _hex(vk.g1_alpha), _hex(vk.g2_beta), _hex(vk.g2_gamma),
                          _hex(vk.g2_delta)])]
     labels += ["vk_gamma_outside", "vk_alpha_off_curve", "vk_no_wires"]
-    text = "\n".join(script) + "\n"
-    outs = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=undefined,address",
-                                       "-fno-sanitize-recover=all"])):
-        exe = _build(tmp, "test_pairing_" + name, flags)
-        out = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0, name + ": " + out.stderr[-4000:]
-        lines = out.stdout.strip().split("\n")
-        assert lines[-1] == "pairing driver ok"
-        outs.append(lines[:-1])
-    assert outs[0] == outs[1], "the sanitized build prints something else"
-    lines = outs[0]
+    _, out, _ = native_build.run_both(native_build.build("test_pairing.cpp", tmp),
+                                      stdin="\n".join(script) + "\n")
+    lines = out.strip().split("\n")
+    assert lines.pop() == "pairing driver ok"
     res = {"consts": lines[:7]}
     assert len(lines) == 7 + len(labels) - 1
     for lab, ln in zip(labels[1:], lines[7:]):

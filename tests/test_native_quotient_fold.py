@@ -3,34 +3,20 @@ fold plan of csrc/quotient_fold.h (what zkmi_pk_load makes of zkmi_pk_desc.fold_
 O and checks it against a dense matrix, 256-bit reference scalars and every refusal; it is built
 plain and with -fsanitize=address,undefined, and the two builds must print the same.  The identity
 the fold rests on is checked here in Python integers, the bases taken as scalars."""
-import os
 import random
-import shutil
-import subprocess
 
 import pytest
 
 from tests import helpers as H
+from tests import native_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = H.R
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@native_build.needs_gxx
 def test_fold_plan_native(tmp_path):
-    outs = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(tmp_path / ("quotient_fold_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "quotient_fold_check.cpp"),
-                               "-o", exe])
-        outs.append(subprocess.check_output([exe], text=True))
-    assert outs[0] == outs[1], "the plain and the sanitized build disagree"
-    assert outs[0].splitlines() == ["ok den", "ok plan terms=23 columns=6", "ok merge bases=9",
-                                    "ok refusals"]
+    _, out, _ = native_build.run_both(native_build.build("quotient_fold_check.cpp", tmp_path))
+    assert out.splitlines() == ["ok den", "ok plan terms=23 columns=6", "ok merge bases=9", "ok refusals"]
 
 
 def _intt(x, w_inv, n, shift_inv=1):

@@ -1,5 +1,5 @@
 """Host build of csrc/r1cs_plan.h for the hints of ZKMI_HINTS_STD (limbs, lookup multiplicities, byte
-operations, commitments): tests/native/r1cs_hints_check.cpp plans a system dumped from compile_circuit
+operations, commitments): tests/native/r1cs_plan_check.cpp plans a system dumped from compile_circuit
 for every number of sub-lanes 0 (auto), 1 .. 64 and interprets the plan on the host, sub-lane by
 sub-lane as r1cs_solve_kernel<S, true> does.  Checked here: wires, a, b, c against the oracle's
 gnark-style solver (cref.r1cs_solve, cref.r1cs_solve_ex -- at a commitment the interpreter is handed
@@ -8,193 +8,25 @@ frontend's; hand-edited descriptions the frontend cannot emit against Python int
 The program is built plain and with -fsanitize=undefined,address; the two builds must agree byte for
 byte."""
 import functools
-import os
 import random
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from gnark_crypto_primitives_amd import groth16
 from gnark_crypto_primitives_amd.frontend import compile_circuit
-from gnark_crypto_primitives_amd.frontend.api import OP_BAND, OP_BXOR
-from gnark_crypto_primitives_amd.frontend.compile import Public, Secret, from_mont_array, to_mont_array
+from gnark_crypto_primitives_amd.frontend.compile import from_mont_array, to_mont_array
 from oracle import cref
 from tests import helpers as H
+from tests.native_build import needs_gxx
+from tests.r1cs_plan_harness import (BASIC, K_BYTEOP, K_COMMIT, K_COUNT, K_LIMBS, LANES_MSG, POW2, RK_COMMIT,
+                                     RK_COUNT_BEGIN, RK_COUNT_END, RK_COUNT_Q, RK_LIMBS, STD, HintsPlain,
+                                     coefficient, description, hint_list, hints_plain_assignments, limbs_of,
+                                     parse, run)
+from tests.r1cs_plan_harness import builds  # noqa: F401 (a fixture)
 from tests.test_commitment import RangeCircuit, TwoCommitments, _mul
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-
-(RK_ASSERT, RK_SOLVE_O, RK_SOLVE_L, RK_SOLVE_R, RK_INVZERO, RK_NBITS, RK_LIMBS, RK_BYTEOP,
- RK_COUNT_BEGIN, RK_COUNT_Q, RK_COUNT_END, RK_COMMIT) = range(12)
-K_LIMBS, K_COUNT, K_COMMIT, K_BYTEOP = 3, 4, 5, 6
-BASIC, STD = 0, 1
-POW2 = (1, 2, 4, 8, 16, 32, 64)
-LANES_MSG = "r1cs solver: lanes_per_proof must be 0 (auto) or a power of two, 1 .. 64"
-
-
-class HintsPlain:
-    """two limb hints, one lookup-multiplicity hint over 53 queries of one or two terms (l0 + 40 is
-    never below 32: counted nowhere), two byte operations over two-term expressions, no commitment"""
-    X = Public()
-    Y = Secret()
-    Z = Secret()
-
-    def define(self, api):
-        l = api.NewHintLimbs(self.Y, 5, 51)
-        api.AssertIsEqual(api.Sum([api.Mul(v, 1 << (5 * i)) for i, v in enumerate(l)]), self.Y)
-        m = api.NewHintLimbs(self.Z, 16, 16)
-        q = list(l) + [api.Add(l[0], 40), api.Add(api.Mul(l[1], 3), l[2])]
-        c = api.NewHintCount(q, 32)
-        x = api.NewHintByteOp(OP_BXOR, api.Add(m[0], api.Mul(m[5], 1 << 16)),
-                              api.Add(l[3], api.Mul(l[4], 256)))
-        a = api.NewHintByteOp(OP_BAND, m[1], m[2])
-        acc = api.Sum([api.Mul(v, i + 1) for i, v in enumerate(c)])
-        api.AssertIsEqual(api.Add(acc, api.Mul(x, 1 << 20), api.Mul(a, 1 << 60), m[3]), self.X)
-
-
-def limbs_of(v, width, count):
-    return [(v >> (width * j)) & ((1 << width) - 1) if width * j < 256 else 0 for j in range(count)]
-
-
-def hints_plain_x(y, z):
-    """the X that satisfies HintsPlain for (Y, Z), with Python integers"""
-    l, m = limbs_of(y, 5, 51), limbs_of(z, 16, 16)
-    q = l + [l[0] + 40, 3 * l[1] + l[2]]
-    c = [sum(1 for v in q if v == j) for j in range(32)]
-    x = ((m[0] + (m[5] << 16)) & 0xffffffff) ^ ((l[3] + l[4] * 256) & 0xffffffff)
-    a = m[1] & m[2]
-    return (sum(v * (i + 1) for i, v in enumerate(c)) + (x << 20) + (a << 60) + m[3]) % H.R
-
-
-def hints_plain_assignments(n, rng):
-    """n assignments: lane 0 has Z = r - 1, lane 7 (if there) a wrong X"""
-    asg = []
-    for i in range(n):
-        y, z = rng.randrange(1 << 253), H.R - 1 if i == 0 else rng.randrange(H.R)
-        asg.append({"X": hints_plain_x(y, z), "Y": y, "Z": z})
-    if n > 7:
-        asg[7]["X"] = (asg[7]["X"] + 1) % H.R
-    return asg
-
-
-@pytest.fixture(scope="module")
-def builds(tmp_path_factory):
-    d = tmp_path_factory.mktemp("r1cs_hints")
-    out = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=undefined,address",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(d / ("r1cs_hints_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "r1cs_hints_check.cpp"),
-                               "-o", exe])
-        out.append(exe)
-    return d, out
-
-
-def hint_list(cc):
-    """[[kind, [expression = [(coefficient index, wire)]], [output wires]]] of a compiled circuit"""
-    kinds, in_ptr, lc_ptr, hcol, hcid, out_ptr, outs = cc.hint_arrays
-    res = []
-    for h, kind in enumerate(kinds.tolist()):
-        exprs = [[(int(hcid[t]), int(hcol[t])) for t in range(lc_ptr[e], lc_ptr[e + 1])]
-                 for e in range(in_ptr[h], in_ptr[h + 1])]
-        res.append([kind, exprs, outs[out_ptr[h]:out_ptr[h + 1]].tolist()])
-    return res
-
-
-def description(cc, inputs, hint_set=STD, hints=None, commit_values=()):
-    """the arrays of the dump, by name, as the test may edit them"""
-    hints = hint_list(cc) if hints is None else hints
-    d = {"header": np.array([cc.n_wires, cc.n_public, cc.n_secret, cc.n_constraints, len(hints), hint_set]),
-         "coeffs": to_mont_array(cc.consts).view(np.uint32).reshape(-1)}
-    for name, (ptr, col, cid) in (("l", cc.L), ("r", cc.Rm), ("o", cc.O)):
-        d[name + "_ptr"] = ptr.copy()
-        d[name + "_terms"] = np.stack([cid, col], axis=1).reshape(-1)
-    in_ptr, lc_ptr, terms, out_ptr, outs = [0], [0], [], [0], []
-    for kind, exprs, ows in hints:
-        for e in exprs:
-            terms += [x for t in e for x in t]
-            lc_ptr.append(len(terms) // 2)
-        in_ptr.append(len(lc_ptr) - 1)
-        outs += ows
-        out_ptr.append(len(outs))
-    d.update(instr=cc.instr.reshape(-1).copy(), hint_kind=np.array([h[0] for h in hints]),
-             hint_in_ptr=np.array(in_ptr), hint_lc_ptr=np.array(lc_ptr), hint_terms=np.array(terms),
-             hint_out_ptr=np.array(out_ptr), hint_out=np.array(outs),
-             inputs=np.ascontiguousarray(inputs).view(np.uint32).reshape(-1),
-             commit_values=np.ascontiguousarray(commit_values, dtype=np.uint64).view(np.uint32).reshape(-1))
-    return d
-
-
-def coefficient(d, value):
-    """index of a coefficient with this value, appended to the description's table"""
-    d["coeffs"] = np.concatenate([d["coeffs"], to_mont_array([value % H.R]).view(np.uint32).reshape(-1)])
-    return d["coeffs"].size // 8 - 1
-
-
-ORDER = ("header", "coeffs", "l_ptr", "l_terms", "r_ptr", "r_terms", "o_ptr", "o_terms", "instr",
-         "hint_kind", "hint_in_ptr", "hint_lc_ptr", "hint_terms", "hint_out_ptr", "hint_out", "inputs",
-         "commit_values")
-
-
-def run(builds, desc, s_first, s_last, tag="case"):
-    """(stdout lines by S, bytes of OUT) -- the same from both builds"""
-    d, exes = builds
-    src = str(d / (tag + ".in"))
-    with open(src, "wb") as f:
-        for name in ORDER:
-            a = np.ascontiguousarray(desc[name], dtype=np.uint32)
-            f.write(np.uint32(a.size).tobytes())
-            f.write(a.tobytes())
-    got = []
-    for exe in exes:
-        dst = str(d / (tag + ".out"))
-        text = subprocess.check_output([exe, src, dst, str(s_first), str(s_last)], text=True)
-        got.append((text, open(dst, "rb").read()))
-    assert got[0] == got[1], "the plain and the sanitized build disagree"
-    lines = {}
-    for line in got[0][0].splitlines():
-        head, rest = line.split(" ", 1)
-        lines[int(head[2:])] = rest
-    assert sorted(lines) == list(range(s_first, s_last + 1))
-    return lines, got[0][1]
-
-
-def parse(blob, n_wires, n_constraints):
-    """[(S, ext, records [n + 1, 8], terms [m, 2], outs, commits [(instruction, record, wire, hashed,
-    private)], n_coeffs, [(status, wires, a, b, c)])]"""
-    w = np.frombuffer(blob, dtype=np.uint32)
-    plans, o = [], 0
-
-    def take(n):
-        nonlocal o
-        r = w[o:o + n]
-        o += n
-        return r
-    while o < w.size:
-        S, ext = (int(x) for x in take(2))
-        recs = take(8 * int(take(1)[0])).reshape(-1, 8)
-        terms = take(2 * int(take(1)[0])).reshape(-1, 2)
-        outs = take(int(take(1)[0]))
-        commits = []
-        for _ in range(int(take(1)[0])):
-            instr, rec, wire = (int(x) for x in take(3))
-            hashed = take(int(take(1)[0])).tolist()
-            commits.append((instr, rec, wire, hashed, take(int(take(1)[0])).tolist()))
-        n_coeffs, batch = (int(x) for x in take(2))
-        sol = []
-        for _ in range(batch):
-            st = int(take(1)[0].astype(np.int32))
-            arrs = [take(8 * n).view(np.uint64).reshape(n, 4)
-                    for n in (n_wires, n_constraints, n_constraints, n_constraints)]
-            sol.append((st, *arrs))
-        plans.append((S, ext, recs, terms, outs, commits, n_coeffs, sol))
-    return plans
+pytestmark = needs_gxx
 
 
 @functools.lru_cache(maxsize=None)

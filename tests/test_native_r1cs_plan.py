@@ -6,10 +6,7 @@ against the frontend's solve_wire; the layout and the padding of the term rows; 
 program is built plain and with -fsanitize=undefined,address; the two builds must agree byte for
 byte."""
 import functools
-import os
 import random
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,98 +18,16 @@ from gnark_crypto_primitives_amd.frontend.compile import to_mont_array
 from gnark_crypto_primitives_amd.tree import smt_witness
 from oracle import cref
 from tests import helpers as H
+from tests.native_build import needs_gxx
+from tests.r1cs_plan_harness import (BASIC, LANES_MSG, POW2, RK_ASSERT, RK_INVZERO, RK_NBITS, RK_SOLVE_L,
+                                     RK_SOLVE_O, RK_SOLVE_R, parse, run)
+from tests.r1cs_plan_harness import builds  # noqa: F401 (a fixture)
+from tests.r1cs_plan_harness import description as std_description
 from tests.test_frontend import Mixed, _mixed_expected
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-
-RK_ASSERT, RK_SOLVE_O, RK_SOLVE_L, RK_SOLVE_R, RK_INVZERO, RK_NBITS = range(6)
-POW2 = (1, 2, 4, 8, 16, 32, 64)
-LANES_MSG = "r1cs solver: lanes_per_proof must be 0 (auto) or a power of two, 1 .. 64"
-
-
-@pytest.fixture(scope="module")
-def builds(tmp_path_factory):
-    d = tmp_path_factory.mktemp("r1cs_plan")
-    out = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=undefined,address",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(d / ("r1cs_plan_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "r1cs_plan_check.cpp"),
-                               "-o", exe])
-        out.append(exe)
-    return d, out
-
-
-def description(cc, inputs):
-    """the arrays of the dump, by name, as the test may edit them"""
-    kinds, in_ptr, lc_ptr, hcol, hcid, out_ptr, outs = cc.hint_arrays
-    d = {"header": np.array([cc.n_wires, cc.n_public, cc.n_secret, cc.n_constraints, len(kinds)]),
-         "coeffs": to_mont_array(cc.consts).view(np.uint32).reshape(-1)}
-    for name, (ptr, col, cid) in (("l", cc.L), ("r", cc.Rm), ("o", cc.O)):
-        d[name + "_ptr"] = ptr.copy()
-        d[name + "_terms"] = np.stack([cid, col], axis=1).reshape(-1)
-    d.update(instr=cc.instr.reshape(-1).copy(), hint_kind=kinds.copy(), hint_in_ptr=in_ptr.copy(),
-             hint_lc_ptr=lc_ptr.copy(), hint_terms=np.stack([hcid, hcol], axis=1).reshape(-1),
-             hint_out_ptr=out_ptr.copy(), hint_out=outs.copy(),
-             inputs=np.ascontiguousarray(inputs).view(np.uint32).reshape(-1))
-    return d
-
-
-ORDER = ("header", "coeffs", "l_ptr", "l_terms", "r_ptr", "r_terms", "o_ptr", "o_terms", "instr",
-         "hint_kind", "hint_in_ptr", "hint_lc_ptr", "hint_terms", "hint_out_ptr", "hint_out", "inputs")
-
-
-def run(builds, desc, s_first, s_last, tag="case"):
-    """(stdout lines by S, bytes of OUT) -- the same from both builds"""
-    d, exes = builds
-    src = str(d / (tag + ".in"))
-    with open(src, "wb") as f:
-        for name in ORDER:
-            a = np.ascontiguousarray(desc[name], dtype=np.uint32)
-            f.write(np.uint32(a.size).tobytes())
-            f.write(a.tobytes())
-    got = []
-    for exe in exes:
-        dst = str(d / (tag + ".out"))
-        text = subprocess.check_output([exe, src, dst, str(s_first), str(s_last)], text=True)
-        got.append((text, open(dst, "rb").read()))
-    assert got[0] == got[1], "the plain and the sanitized build disagree"
-    lines = {}
-    for line in got[0][0].splitlines():
-        head, rest = line.split(" ", 1)
-        lines[int(head[2:])] = rest
-    assert sorted(lines) == list(range(s_first, s_last + 1))
-    return lines, got[0][1]
-
-
-def parse(blob, cc):
-    """[(S, records [n + 1, 8], terms [m, 2], outs, n_coeffs, [(status, wires, a, b, c)])]"""
-    w = np.frombuffer(blob, dtype=np.uint32)
-    plans, o = [], 0
-
-    def take(n):
-        nonlocal o
-        r = w[o:o + n]
-        o += n
-        return r
-    while o < w.size:
-        S = int(take(1)[0])
-        recs = take(8 * int(take(1)[0])).reshape(-1, 8)
-        terms = take(2 * int(take(1)[0])).reshape(-1, 2)
-        outs = take(int(take(1)[0]))
-        n_coeffs, batch = (int(x) for x in take(2))
-        sol = []
-        for _ in range(batch):
-            st = int(take(1)[0].astype(np.int32))
-            arrs = [take(8 * n).view(np.uint64).reshape(n, 4)
-                    for n in (cc.n_wires, cc.n_constraints, cc.n_constraints, cc.n_constraints)]
-            sol.append((st, *arrs))
-        plans.append((S, recs, terms, outs, n_coeffs, sol))
-    return plans
+pytestmark = needs_gxx
+# every system here is dumped under ZKMI_HINTS_BASIC, without commitment values
+description = functools.partial(std_description, hint_set=BASIC)
 
 
 @functools.lru_cache(maxsize=None)
@@ -245,21 +160,22 @@ def test_plans_solve_like_the_oracle(builds, name, n_constraints):
     cc, inputs = _case(name)
     assert cc.n_constraints == n_constraints
     lines, blob = run(builds, description(cc, inputs), 0, 64, name)
-    plans = parse(blob, cc)
+    plans = parse(blob, cc.n_wires, cc.n_constraints)
     assert [p[0] for p in plans] == [plans[0][0], *POW2]          # auto first, then 1 .. 64
     rh = cref.R1csHandle(cc)
     want = [cref.r1cs_solve(rh, x) for x in inputs]
     assert [rc != 0 for rc, *_ in want] == [False] * (len(want) - 1 - (name == "mixed")) + \
         [True] * (1 + (name == "mixed"))
     kinds_seen = set()
-    for n, (S, recs, terms, outs, n_coeffs, sol) in enumerate(plans):
+    for n, (S, ext, recs, terms, outs, commits, n_coeffs, sol) in enumerate(plans):
+        assert ext == 0 and not commits
         total, longest = check_plan(cc, S, recs, terms, outs, n_coeffs)
         kinds_seen |= set(recs[:-1, 0].tolist())
         if n == 0:
             assert S == auto_lanes(total, cc.instr.shape[0])
         inversions = int(np.isin(recs[:-1, 0], (RK_SOLVE_L, RK_SOLVE_R, RK_INVZERO)).sum())
         assert lines[S if n else 0].startswith(
-            "ok lanes=%d instr=%d terms=%d longest=%d inversions=%d plan_terms=%d coeffs=%d "
+            "ok lanes=%d emul=0 instr=%d terms=%d longest=%d inversions=%d plan_terms=%d coeffs=%d "
             % (S, cc.instr.shape[0], total, longest, inversions, terms.shape[0], n_coeffs))
         for (st, w, a, b, c), (rc, w0, a0, b0, c0) in zip(sol, want):
             assert (st != 0) == (rc != 0) and st in (0, -5)
@@ -274,7 +190,7 @@ def test_plans_solve_like_the_oracle(builds, name, n_constraints):
     if name == "elgamal-add":
         assert RK_SOLVE_L in kinds_seen
     if name == "smt8":
-        assert max(int(r[5] + r[6]) * p[0] for p in plans[:1] for r in p[1]) >= 123
+        assert max(int(r[5] + r[6]) * p[0] for p in plans[:1] for r in p[2]) >= 123
 
 
 def _insert_term(d, m, row, cid, wire):

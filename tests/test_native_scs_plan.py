@@ -6,104 +6,20 @@ an input) and interprets it with ff.h.  Checked here: the wires against the Pyth
 (ScsCircuit.solve_description), a hand-built system that exercises every position of the unknown,
 every refusal.  The program is built plain and with -fsanitize=address,undefined; the two builds must
 print the same."""
-import os
 import random
-import shutil
-import subprocess
-import types
 
 import numpy as np
-import pytest
 
 from gnark_crypto_primitives_amd import circuits
 from gnark_crypto_primitives_amd.frontend.compile import to_mont_array
-from gnark_crypto_primitives_amd.frontend.scs import ScsCircuit, compile_scs
+from gnark_crypto_primitives_amd.frontend.scs import compile_scs
 from gnark_crypto_primitives_amd.tree import smt_witness
-from tests import helpers as H
+from tests.native_build import needs_gxx
+from tests.scs_plan_harness import LANES_MSG, NONE, POW2, R, Hand, dump_of, hand_inputs, refusal, run, words
+from tests.scs_plan_harness import builds  # noqa: F401 (a fixture)
 from tests.test_frontend import Mixed, _mixed_expected
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-R = H.R
-NONE = 0xFFFFFFFF
-POW2 = (1, 2, 4, 8, 16, 32, 64)
-LANES_MSG = "scs solver: lanes_per_proof must be 0 (auto) or a power of two, 1 .. 64"
-
-
-@pytest.fixture(scope="module")
-def builds(tmp_path_factory):
-    d = tmp_path_factory.mktemp("scs_plan")
-    out = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(d / ("scs_plan_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "scs_plan_check.cpp"),
-                               "-o", exe])
-        out.append(exe)
-    return d, out
-
-
-def words(ints):
-    return to_mont_array([int(v) % R for v in ints]).view(np.uint32).reshape(-1) if len(ints) else \
-        np.zeros(0, np.uint32)
-
-
-def dump_of(system, desc, inputs):
-    """the arrays of the dump, by name, as the test may edit them"""
-    xa, xb, xc, _ = system.wiring()
-    ng = len(xa)
-    sel = np.concatenate([words([int(v) for v in col[:ng]])
-                          for col in (system.qL, system.qR, system.qO, system.qM, system.qC)])
-    return {"header": np.array([desc["n_wires"], ng, system.n_public - 1, len(desc["input_wire"]),
-                                len(desc["hint_kind"]), 0]),
-            "xa": xa.copy(), "xb": xb.copy(), "xc": xc.copy(), "sel": sel,
-            "input_wire": desc["input_wire"].copy(), "instr": desc["instr"].reshape(-1).copy(),
-            "hint_kind": desc["hint_kind"].copy(), "hint_in_ptr": desc["hint_in_ptr"].copy(),
-            "hint_in_wire": desc["hint_in_wire"].copy(), "hint_in_coef": words(desc["hint_in_coef"]),
-            "hint_out_ptr": desc["hint_out_ptr"].copy(), "hint_out": desc["hint_out"].copy(),
-            "inputs": np.concatenate([words(x) for x in inputs]) if inputs else np.zeros(0, np.uint32)}
-
-
-ORDER = ("header", "xa", "xb", "xc", "sel", "input_wire", "instr", "hint_kind", "hint_in_ptr",
-         "hint_in_wire", "hint_in_coef", "hint_out_ptr", "hint_out", "inputs")
-
-
-def run(builds, dump, s_first, s_last, tag="case"):
-    """(stdout by S, [(S, [(status, wires [n_wires, 4])])]) -- the same from both builds"""
-    d, exes = builds
-    src = str(d / (tag + ".in"))
-    with open(src, "wb") as f:
-        for name in ORDER:
-            a = np.ascontiguousarray(dump[name], dtype=np.uint32)
-            f.write(np.uint32(a.size).tobytes())
-            f.write(a.tobytes())
-    got = []
-    for exe in exes:
-        dst = str(d / (tag + ".out"))
-        p = subprocess.run([exe, src, dst, str(s_first), str(s_last)], text=True, capture_output=True)
-        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
-        got.append((p.stdout, open(dst, "rb").read()))
-    assert got[0] == got[1], "the plain and the sanitized build disagree"
-    lines = {}
-    for line in got[0][0].splitlines():
-        head, rest = line.split(" ", 1)
-        lines[int(head[2:])] = rest
-    assert sorted(lines) == list(range(s_first, s_last + 1))
-    w = np.frombuffer(got[0][1], dtype=np.uint32)
-    n_wires, plans, o = int(dump["header"][0]), [], 0
-    while o < w.size:
-        S, batch = int(w[o]), int(w[o + 1])
-        o += 2
-        sol = []
-        for _ in range(batch):
-            sol.append((int(w[o:o + 1].view(np.int32)[0]),
-                        w[o + 1:o + 1 + 8 * n_wires].view(np.uint64).reshape(n_wires, 4)))
-            o += 1 + 8 * n_wires
-        plans.append((S, sol))
-    return lines, plans
+pytestmark = needs_gxx
 
 
 def every_lane_count(builds, system, desc, inputs, want_status, tag):
@@ -119,8 +35,8 @@ def every_lane_count(builds, system, desc, inputs, want_status, tag):
         if s and s not in POW2:
             assert lines[s] == "error: " + LANES_MSG
             continue
-        ok, lanes, records, steps, levels, inversions = lines[s].split()
-        assert ok == "ok" and (int(lanes) == s or (s == 0 and int(lanes) in (1, 2, 4, 8, 16)))
+        ok, lanes, records, steps, levels, inversions, std, _ = lines[s].split()
+        assert ok == "ok" and std == "0" and (int(lanes) == s or (s == 0 and int(lanes) in (1, 2, 4, 8, 16)))
         assert int(steps) >= int(levels) >= 1 and int(steps) * int(lanes) >= int(records)
     for S, sol in plans:
         for i, (status, wires) in enumerate(sol):
@@ -150,50 +66,6 @@ def test_smt8_every_lane_count(builds):
     every_lane_count(builds, sc, sc.solver_description(), inputs, [0], "smt8")
 
 
-class Hand:
-    """A hand-built system: the unknown in column a alone, b alone, c alone and in all three; a DIV
-    with the unknown in b and one in a without a linear part; marked (+1 / -1) and unmarked selectors
-    on the unknown; a constant hint input; InvZero of zero; NBits over two records; an assertion."""
-    n_public = 2          # counting ONE, as ScsCircuit does: one public input
-    #        a   b   c   qL  qR  qO  qM  qC
-    gates = [(0, 0, 0, 1, 0, 0, 0, 0),            # public input p = wire 0
-             (2, 2, 2, 1, 0, 0, 0, -1),           # w2 = 1: all three positions, k = 1 (marked)
-             (3, 1, 0, 5, 1, -1, 0, 7),           # a alone, unmarked 5 on the unknown
-             (1, 4, 3, 1, -1, 2, 0, 0),           # b alone, marked -1 on the unknown
-             (3, 4, 5, 0, 0, -1, 3, 0),           # c alone, behind an unmarked product
-             (5, 6, 4, 2, 3, -1, 1, 0),           # DIV, unknown in b: -(2 w5 - w4) / (3 + w5)
-             (7, 5, 1, 0, 0, -1, 1, 0),           # DIV, unknown in a, k = 0: w1 / w5
-             (29, 7, 2, 0, 0, -1, 1, 0),          # an assertion: w29 w7 = 1
-             (30, 30, 30, 1, 0, 0, 0, 0),         # w30 = 0
-             (32, 32, 7, 2, 3, 1, 0, 0)]          # a and b together, qM = 0: 5 x + w7 = 0
-    n_gates = len(gates)
-    n_wires = 33
-
-    def __init__(self):
-        col = lambda j: np.array([g[j] % R for g in self.gates], dtype=object)
-        self.qL, self.qR, self.qO, self.qM, self.qC = (col(j) for j in (3, 4, 5, 6, 7))
-
-    def wiring(self):
-        x = [np.array([g[j] for g in self.gates], dtype=np.uint32) for j in range(3)]
-        return x[0], x[1], x[2], self.n_wires
-
-    solve_description = ScsCircuit.solve_description
-
-    def description(self):
-        u32 = lambda x: np.array(x, dtype=np.uint32)
-        instr = [(0, 0), (0, 1), (0, 2), (0, 3), (0, 4), (0, 5), (0, 6), (1, 0), (1, 1), (1, 2), (0, 7),
-                 (0, 8), (1, 3), (0, 9)]
-        return {"n_wires": self.n_wires, "input_wire": u32([0, 1, NONE]), "instr": u32(instr),
-                "hint_kind": u32([2, 1, 1, 1]), "hint_in_ptr": u32([0, 1, 2, 3, 4]),
-                "hint_in_wire": u32([1, NONE, 7, 30]), "hint_in_coef": [3, 9, 1, 1],
-                "hint_out_ptr": u32([0, 20, 21, 22, 23]),
-                "hint_out": u32(list(range(8, 28)) + [28, 29, 31])}
-
-
-def hand_inputs(rng):
-    return [rng.randrange(R), rng.randrange(1 << 18), rng.randrange(R)]
-
-
 def test_hand_built_system_every_lane_count(builds):
     rng = random.Random(13)
     hand = Hand()
@@ -211,13 +83,6 @@ def test_hand_built_system_every_lane_count(builds):
     assert w[8:28] == [(3 * s >> j) & 1 for j in range(20)] and w[28] == inv(9)
     assert w[29] == inv(w[7]) and w[30] == 0 and w[31] == 0 and w[32] == -w[7] * inv(5) % R
     every_lane_count(builds, hand, desc, inputs, [0, 0, 0], "hand")
-
-
-def refusal(builds, dump, tag, lanes=4):
-    lines, plans = run(builds, dump, lanes, lanes, tag)
-    assert not plans
-    assert lines[lanes].startswith("error: scs solver: "), lines[lanes]
-    return lines[lanes][len("error: scs solver: "):]
 
 
 def test_refusals(builds):

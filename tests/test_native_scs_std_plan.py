@@ -1,169 +1,27 @@
-"""Host build of csrc/scs_plan.h under ZKMI_HINTS_STD: tests/native/scs_plan_std_check.cpp builds the
+"""Host build of csrc/scs_plan.h under ZKMI_HINTS_STD: tests/native/scs_plan_check.cpp builds the
 plan of a hand-written description for every number of sub-lanes 0 (auto), 1 .. 64, asserts the
 plan's two guarantees on every step -- a lookup count's three phases and the boundaries of the
 commitment hints with them -- and interprets it with scs_record_run.  Checked here: the wires against
 the Python reference (ScsCircuit.solve_description), the boundaries, every new refusal, and that a
 description without a std kind gives the same plan under both sets.  The program is built plain and
 with -fsanitize=address,undefined; the two builds must print the same."""
-import os
 import random
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from gnark_crypto_primitives_amd.frontend.compile import to_mont_array
-from gnark_crypto_primitives_amd.frontend.scs import ScsCircuit
-from tests import helpers as H
-from tests.test_native_scs_plan import ORDER, POW2, LANES_MSG, Hand, dump_of, hand_inputs, words
+from tests.native_build import needs_gxx
+from tests.scs_plan_harness import (LANES_MSG, NONE, POW2, STD, R, Hand, HandStd, dump_of, hand_inputs, refusal,
+                                    run, stand_in, std_inputs)
+from tests.scs_plan_harness import builds  # noqa: F401 (a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-R = H.R
-NONE = 0xFFFFFFFF
+pytestmark = needs_gxx
 
 
-class HandStd:
-    """A hand-written system for the hints of ZKMI_HINTS_STD.  Inputs: the public p (wire 0), s
-    (wire 1), t (wire 2) and one that no gate reads.
-      limbs      width 8 of s, 5 outputs; width 64 of 3 t, 5 outputs (the last one lies past bit 256)
-      counts     a table of 17 (one chunk of 16 and 1) with 7 queries -- limbs (mostly >= 17: they
-                 count nowhere), the constant 5, 2 * ONE, ONE --; a table of 5 on the same levels
-                 with a query >= its size; a table of 2 with no query
-      byte ops   XOR of s and 5 t (field elements: bits above 32 set), AND of a 64-bit limb and a
-                 48-bit constant
-      commitments (``commits=True``): 0 over inputs only (its first range of steps is empty), 1 over
-                 the first one's wire and a wire deep in the solve, 2 over the last wire solved
-                 (nothing depends on it: the last range is empty)"""
-    n_public = 2          # counting ONE
-    BASE = [(0, 0, 0, 1, 0, 0, 0, 0),               # public input p = wire 0
-            (3, 3, 3, 1, 0, 0, 0, -1),              # ONE = wire 3
-            (38, 39, 40, 1, 1, -1, 0, 0),           # w40 = xor + and
-            (40, 14, 41, 0, 0, -1, 1, 0)]           # w41 = w40 * (count of 0 in the table of 17)
-    COMMIT = [(1, 1, 1, -1, 0, 0, 0, 0), (2, 2, 2, -1, 0, 0, 0, 0),      # rows 4, 5: C_0
-              (42, 42, 42, -1, 0, 0, 0, 0),                              # row 6: r_0, wire 42
-              (42, 42, 42, -1, 0, 0, 0, 0), (41, 41, 41, -1, 0, 0, 0, 0),  # rows 7, 8: C_1
-              (43, 43, 43, -1, 0, 0, 0, 0),                              # row 9: r_1, wire 43
-              (43, 42, 44, 1, 1, -1, 0, 0),                              # row 10: w44 = w43 + w42
-              (44, 44, 44, -1, 0, 0, 0, 0),                              # row 11: C_2
-              (45, 45, 45, -1, 0, 0, 0, 0)]                              # row 12: r_2, wire 45
-
-    def __init__(self, commits=True):
-        self.with_commits = commits
-        self.gates = self.BASE + (self.COMMIT if commits else [])
-        self.n_gates = len(self.gates)
-        self.n_wires = 46 if commits else 42
-        self.commitments = [{"rows": [4, 5], "row": 6}, {"rows": [7, 8], "row": 9},
-                            {"rows": [11], "row": 12}] if commits else []
-        col = lambda j: np.array([g[j] % R for g in self.gates], dtype=object)
-        self.qL, self.qR, self.qO, self.qM, self.qC = (col(j) for j in (3, 4, 5, 6, 7))
-        # (kind, [(wire | NONE, coefficient)], outputs)
-        self.hints = [
-            (3, [(NONE, 8), (1, 1)], list(range(4, 9))),
-            (3, [(NONE, 64), (2, 3)], list(range(9, 14))),
-            (4, [(NONE, 17), (4, 1), (5, 1), (6, 1), (NONE, 5), (3, 2), (3, 1), (8, 1)], list(range(14, 31))),
-            (4, [(NONE, 5), (3, 1), (3, 1), (NONE, 7), (3, 4)], list(range(31, 36))),
-            (4, [(NONE, 2)], [36, 37]),
-            (6, [(NONE, 1), (1, 1), (2, 5)], [38]),
-            (6, [(NONE, 2), (9, 1), (NONE, 0xFFFF0000FFFF)], [39])]
-        self.instr = [(0, 0), (0, 1)] + [(1, h) for h in range(7)] + [(0, 2), (0, 3)]
-        if commits:
-            self.hints += [(5, [(NONE, 0), (1, 1), (2, 1)], [42]), (5, [(NONE, 1), (42, 1), (41, 1)], [43]),
-                           (5, [(NONE, 2), (44, 1)], [45])]
-            self.instr += [(0, 4), (0, 5), (1, 7), (0, 6), (0, 7), (0, 8), (1, 8), (0, 9), (0, 10), (0, 11),
-                           (1, 9), (0, 12)]
-
-    def wiring(self):
-        x = [np.array([g[j] for g in self.gates], dtype=np.uint32) for j in range(3)]
-        return x[0], x[1], x[2], self.n_wires
-
-    solve_description = ScsCircuit.solve_description
-
-    def description(self, hints=None, instr=None, n_wires=None):
-        hints = self.hints if hints is None else hints
-        u32 = lambda x: np.array(x, dtype=np.uint32)
-        in_ptr, out_ptr = [0], [0]
-        for _, ins, outs in hints:
-            in_ptr.append(in_ptr[-1] + len(ins))
-            out_ptr.append(out_ptr[-1] + len(outs))
-        return {"hint_set": 1, "n_wires": self.n_wires if n_wires is None else n_wires,
-                "input_wire": u32([0, 1, 2, NONE]),
-                "instr": u32(self.instr if instr is None else instr).reshape(-1, 2),
-                "hint_kind": u32([k for k, _, _ in hints]), "hint_in_ptr": u32(in_ptr),
-                "hint_in_wire": u32([w for _, ins, _ in hints for w, _ in ins]),
-                "hint_in_coef": [c for _, ins, _ in hints for _, c in ins],
-                "hint_out_ptr": u32(out_ptr), "hint_out": u32([o for _, _, outs in hints for o in outs])}
-
-    def skip_rows(self):
-        return [r for c in self.commitments for r in c["rows"] + [c["row"]]]
-
-
-def stand_in(i, vals):
-    """the challenge scs_plan_std_check.cpp gives commitment i"""
-    return (1 + i + sum((j + 1) * v for j, v in enumerate(vals))) % R
-
-
-def std_inputs(rng):
-    return [rng.randrange(R), rng.randrange(R), rng.randrange(R), rng.randrange(R)]
-
-
-@pytest.fixture(scope="module")
-def builds(tmp_path_factory):
-    d = tmp_path_factory.mktemp("scs_std_plan")
-    out = []
-    for name, flags in (("plain", ["-O2"]),
-                        ("sanitized", ["-O1", "-g", "-fsanitize=address,undefined",
-                                       "-fno-sanitize-recover=all"])):
-        exe = str(d / ("scs_plan_std_check_" + name))
-        subprocess.check_call(["g++", "-std=c++17", *flags, "-I",
-                               os.path.join(ROOT, "gnark_crypto_primitives_amd", "csrc"),
-                               os.path.join(ROOT, "tests", "native", "scs_plan_std_check.cpp"),
-                               "-o", exe])
-        out.append(exe)
-    return d, out
-
-
-def std_dump(system, desc, inputs, hint_set=1):
-    d = dump_of(system, desc, inputs)
-    d["header"][5] = hint_set
-    d["skip_rows"] = np.array(system.skip_rows() if hasattr(system, "skip_rows") else [], dtype=np.uint32)
-    return d
-
-
-def run(builds, dump, s_first, s_last, tag="case"):
-    """(stdout by S, [(S, [(status, wires [n_wires, 4])])]) -- the same from both builds"""
-    d, exes = builds
-    src = str(d / (tag + ".in"))
-    with open(src, "wb") as f:
-        for name in ORDER + ("skip_rows",):
-            a = np.ascontiguousarray(dump[name], dtype=np.uint32)
-            f.write(np.uint32(a.size).tobytes())
-            f.write(a.tobytes())
-    got = []
-    for exe in exes:
-        dst = str(d / (tag + ".out"))
-        p = subprocess.run([exe, src, dst, str(s_first), str(s_last)], text=True, capture_output=True)
-        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
-        got.append((p.stdout, open(dst, "rb").read()))
-    assert got[0] == got[1], "the plain and the sanitized build disagree"
-    lines = {}
-    for line in got[0][0].splitlines():
-        head, rest = line.split(" ", 1)
-        lines[int(head[2:])] = rest
-    assert sorted(lines) == list(range(s_first, s_last + 1))
-    w = np.frombuffer(got[0][1], dtype=np.uint32)
-    n_wires, plans, o = int(dump["header"][0]), [], 0
-    while o < w.size:
-        S, batch = int(w[o]), int(w[o + 1])
-        o += 2
-        sol = []
-        for _ in range(batch):
-            sol.append((int(w[o:o + 1].view(np.int32)[0]),
-                        w[o + 1:o + 1 + 8 * n_wires].view(np.uint64).reshape(n_wires, 4)))
-            o += 1 + 8 * n_wires
-        plans.append((S, sol))
-    return lines, plans
+def std_dump(system, desc, inputs, hint_set=STD):
+    """the dump for a caller that can run ZKMI_HINTS_STD"""
+    return dump_of(system, desc, inputs, hint_set, max_set=STD)
 
 
 def test_the_reference_itself():
@@ -245,13 +103,6 @@ def test_a_basic_description_gives_the_same_plan_under_both_sets(builds):
     b, pb = run(builds, std_dump(hand, desc, inputs, 1), 0, 64, "basic1")
     assert a == b and a[4].split()[0] == "ok" and a[4].split()[6] == "0"
     assert all(np.array_equal(x[1][0][1], y[1][0][1]) for x, y in zip(pa, pb))
-
-
-def refusal(builds, dump, tag, lanes=4):
-    lines, plans = run(builds, dump, lanes, lanes, tag)
-    assert not plans
-    assert lines[lanes].startswith("error: scs solver: "), lines[lanes]
-    return lines[lanes][len("error: scs solver: "):]
 
 
 def test_refusals(builds):
